@@ -1,9 +1,16 @@
 """
 bench.py — env-steps/s of the batched LocoEnv.step() hot path (BASELINE.json metric) on N GPUs of one node.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--envs-per-gpu 4096] [--task UnitreeA1.simple]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--envs-per-gpu 4096] [--task UnitreeA1.simple] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up (W control steps), times exactly K control steps, writes the outputs of that block when
+`--dump-outputs DIR` is given (dump_outputs: final qpos / qvel and the block's counters as DIR/<name>.npy; the inputs are
+seeded, so two builds can be compared output for output) and prints the line: `value` = env-steps/s of the K-step block,
+`ms_per_step` = milliseconds of one of its control steps. `--full` adds every other leg described below (the sustained
+block, the fused rollout, the parity sample against the fp64 oracle, the CPU baseline, the python_surface leg and the other
+BASELINE configs); each of them can also be asked for on its own by its option.
 
 `--gpus N` with N > 1 and no launcher around it (WORLD_SIZE unset): bench.py starts the N ranks itself (one process per
 GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, rendezvous on 127.0.0.1) and fails loudly on a node with fewer GPUs.
@@ -16,22 +23,22 @@ environment (= 10 physics substeps + observation + reward + termination + resets
 Environments are independent: ranks shard them (weak scaling), the only collective is the metric
 all-reduce at report time: ncclAllReduce on librccl.so through ctypes (loco_mujoco_amd/utils/collective.py).
 
-The other BASELINE configs ride in the same line under "configs" (one rank, default task only): short legs of
+With --full, the other BASELINE configs ride in the same line under "configs" (one rank, default task only): short legs of
 HumanoidTorque.run (4096, random policy), Atlas.walk with back joints and per-episode joint-damping randomisation (2048 =
 config 4's per-GPU share) and HumanoidMuscle.run (2048 = config 5's per-GPU share), each with its own kernel time, roofline,
 parity sample against the fp64 oracle and the number of control steps the replay kernel ran. `--task` runs any of them as
 the main leg instead (side measurements; the driver's default run is the A1 line).
 
 The timed region holds inputs resident in HBM (state lives on the device); it is bracketed by a barrier +
-device synchronisation on both sides, the maximum over ranks is taken. `value` is the rate of the LONGER of the two
-per-step blocks (`--steps` and `--sustained`): a 20-step burst reads several per cent faster than steady state, and the
-headline is the conservative one; the burst is reported beside it.
+device synchronisation on both sides, the maximum over ranks is taken. When the sustained block runs (--full, or
+`--sustained`), `value` is the rate of the LONGER of the two per-step blocks (`--steps` and `--sustained`): a 20-step burst
+reads several per cent faster than steady state, and the headline is the conservative one; the burst is reported beside it.
 roofline: this path is not HBM-bound; `achieved` = algorithmic bytes per launch
 (636 B per env-step incl. warm start x envs) / mean kernel duration measured with HIP events on the
 library's own stream (lm_rollout returns it), against the 8 TB/s HBM peak — expect ~1e-4..1e-3. What binds is the
 FP32 vector pipe at one wave per SIMD: `roofline.binding` carries the VALU issue fraction and the FP32 flop fraction
 (counted flops per env-step from the committed profile's instruction counts and the kernel's static instruction mix).
-cpu_baseline: the fp64 C oracle restatement ("port") on every host core, on a bounded sample of the same workload
+cpu_baseline (--full): the fp64 C oracle restatement ("port") on every host core, on a bounded sample of the same workload
 (rank 0, N=1 only).
 """
 
@@ -343,6 +350,36 @@ def timed_leg(W, coll, n_steps, seed, steps_per_launch=1):
     return dt, stats
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+DUMP_STATS = ("env_steps", "episodes", "reward_sum", "nan_resets", "overflow_contacts", "unhandled_geoms", "self_contacts")
+
+
+def dump_outputs(W, st, out_dir, rank, world):
+    """`--dump-outputs DIR`: what a caller of the timed path (lm_rollout) holds after its last control step, as DIR/<name>.npy —
+    qpos / qvel [envs, nq / nv] (float32 as the device keeps them), act [envs, na] (muscle tasks), flags [envs] (lm_get_flags of the
+    last control step, as float32) and stats (float64: the block's counters in the order of DUMP_STATS; its kernel time is left
+    out). Above 64 MB in all (over the ranks), a fixed sample of environments (RandomState(0), sorted ids in env_index.npy) is written instead.
+    With more than one rank every rank writes its own share as <name>.rank<r>.npy."""
+    b = W.b
+    q, v = b.get_state()
+    arrays = {"qpos": q, "qvel": v}
+    if b.na:
+        arrays["act"] = b.get_activation()
+    arrays["flags"] = b.flags().astype(np.float32)
+    per_env = sum(a.nbytes for a in arrays.values()) / W.n
+    limit = DUMP_LIMIT_BYTES // world - 4096                   # every rank its share; 4 KB for the .npy headers and the stats
+    if W.n * per_env > limit:
+        keep = int(limit // (per_env + 8))
+        idx = np.sort(np.random.RandomState(0).choice(W.n, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["env_index"] = (idx + W.offset).astype(np.float64)
+    arrays["stats"] = np.array([st[k] for k in DUMP_STATS], dtype=np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = ".rank%d" % rank if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), np.ascontiguousarray(a))
+
+
 def lib_sha16():
     from loco_mujoco_amd import backend as _backend
     return hashlib.sha256(open(_backend.LIB_PATH, "rb").read()).hexdigest()[:16]
@@ -550,18 +587,33 @@ def main():
                     "communicator does not come up (N > 1). The DEFAULT whenever WORLD_SIZE > 1 and every rank has a GPU of its own")
     ap.add_argument("--allow-tcp-fallback", action="store_true", help="N > 1: let the metric reduction fall back to the rendezvous sockets "
                     "when the RCCL communicator does not come up (the bench line names the transport in config.collective)")
-    ap.add_argument("--sustained", type=int, default=200, help="control steps of the sustained leg (per-step launches, one "
+    ap.add_argument("--full", action="store_true", help="everything beside the headline as well: the sustained block, the fused-rollout "
+                    "leg, the parity sample against the fp64 oracle (exit 3 beyond the tolerance), the CPU baseline, the python_surface "
+                    "leg and the other BASELINE configs. Without it a run sets up, warms up, times the --steps block and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the --steps block, write what it computed (final "
+                    "qpos / qvel, muscle activations, validity flags, the block's counters) as DIR/<name>.npy for output-for-output "
+                    "comparisons of two builds")
+    ap.add_argument("--sustained", type=int, default=None, help="control steps of the sustained leg (per-step launches, one "
                     "timed block of at least this many steps; 0 = skip; skipped when --steps already covers it). When it runs, "
-                    "`value` is ITS rate (the conservative one) and the --steps block is reported as `burst`")
+                    "`value` is ITS rate (the conservative one) and the --steps block is reported as `burst`. Default: 200 with --full, else 0")
     ap.add_argument("--no-pollers", action="store_true", help="profiling runs (rocprofv3 runs one kernel at a time): the replay kernel only as the "
                     "pass behind the regular launch, no polling workgroups beside it (lm_batch_set_replay(3))")
-    ap.add_argument("--fuse", type=int, default=25, help="control steps per launch of the extra fused-rollout leg (0/1 = skip)")
-    ap.add_argument("--configs", default="auto", choices=["auto", "on", "off"], help="short legs of the other BASELINE configs "
-                    "(HumanoidTorque.run, Atlas.walk --dr 2048, HumanoidMuscle.run 2048) under the `configs` key; auto = one rank, default task")
-    ap.add_argument("--surface-steps", type=int, default=200, help="calls of LocoEnv.step() of the `python_surface` leg (0 = skip; one rank, default task)")
+    ap.add_argument("--fuse", type=int, default=None, help="control steps per launch of the extra fused-rollout leg (0/1 = skip). "
+                    "Default: 25 with --full, else 0")
+    ap.add_argument("--configs", default=None, choices=["auto", "on", "off"], help="short legs of the other BASELINE configs "
+                    "(HumanoidTorque.run, Atlas.walk --dr 2048, HumanoidMuscle.run 2048) under the `configs` key; auto = one rank, default task. "
+                    "Default: auto with --full, else off")
+    ap.add_argument("--surface-steps", type=int, default=None, help="calls of LocoEnv.step() of the `python_surface` leg (0 = skip; one rank, "
+                    "default task). Default: 200 with --full, else 0")
     ap.add_argument("--config-steps", type=int, default=60)
     ap.add_argument("--config-warmup", type=int, default=20)
     args = ap.parse_args()
+    # the legs beside the headline: on with --full, off in a plain run; an explicit option wins either way
+    for name, full_default, plain_default in (("sustained", 200, 0), ("fuse", 25, 0), ("configs", "auto", "off"), ("surface_steps", 200, 0)):
+        if getattr(args, name) is None:
+            setattr(args, name, full_default if args.full else plain_default)
+    # the parity sample and the CPU baseline: --full only (--no-cpu-baseline drops them there too)
+    checks = args.full and not args.no_cpu_baseline
 
     if args.cpu_worker:
         env = make_env(args.task, args.dr)
@@ -609,6 +661,8 @@ def main():
 
     b.rollout(args.warmup, action_mode=W.action_mode, seed=11)
     elapsed, st = timed_leg(W, coll, args.steps, 12)
+    if args.dump_outputs:                                     # what the --steps block computed, before any other leg moves the state
+        dump_outputs(W, st, args.dump_outputs, rank, world)
 
     # extra leg, reported beside `value`, never as `value`: the same number of control steps with --fuse steps per launch
     # (lm_rollout_fused: no device-wide join between control steps; bitwise the same results). Continues from the state
@@ -672,7 +726,8 @@ def main():
                                   "tcp": "socket reduction of 17 doubles at report time (RCCL not used)"}[coll.backend],
                    "ranks_seen_by_rccl": ranks_rccl,
                    "value_is": ("the sustained block: %d per-step launches after the --steps block (same policy, same state mixture); the --steps "
-                                "block is `burst`" % args.sustained) if main_steps != args.steps else "the --steps block (it covers --sustained)"},
+                                "block is `burst`" % args.sustained) if main_steps != args.steps else
+                               "the --steps block" + (" (it covers --sustained)" if args.sustained else "")},
         "roofline": roof,
         "stats": {"episodes": vals[2], "mean_reward": vals[3] / max(env_steps, 1), "nan_resets": vals[4],
                   "overflow_contacts": vals[5], "unhandled_geom_substeps": vals[6],
@@ -697,9 +752,10 @@ def main():
                                 "note": "policy-free rollout with %d control steps per launch (lm_rollout_fused): every "
                                         "environment advances on its own, results bitwise those of single-step launches; "
                                         "a policy in the loop gets `value`" % args.fuse}
-    out["sustained"] = {"steps": main_steps, "value": value, "unit": "env-steps/s", "ms_per_step": main_leg["ms_per_step"],
-                        "note": "= `value`"}
-    if world == 1 and not args.no_cpu_baseline:
+    if args.sustained > 0:
+        out["sustained"] = {"steps": main_steps, "value": value, "unit": "env-steps/s", "ms_per_step": main_leg["ms_per_step"],
+                            "note": "= `value`"}
+    if world == 1 and checks:
         out["parity"] = parity_sample(W, not W.default_task)
         one = cpu_baseline(env, W.table, args.task, not W.default_task, budget_s=6.0)
         allc = cpu_baseline_all_cores(args.task, not W.default_task, args.dr)
@@ -735,7 +791,7 @@ def main():
         out["configs"] = {}
         for cfg in SIDE_CONFIGS:
             try:
-                res = side_config(cfg, rank, local_rank, args.config_steps, args.config_warmup, lib_sha, with_cpu=not args.no_cpu_baseline)
+                res = side_config(cfg, rank, local_rank, args.config_steps, args.config_warmup, lib_sha, with_cpu=checks)
             except Exception as e:      # noqa: BLE001 - a failing side leg is reported in the line, and fails the run
                 res = {"error": "%s: %s" % (type(e).__name__, e)}
                 parity_ok = False

@@ -1589,13 +1589,13 @@ def test_bench_two_ranks_on_one_gpu_shard_invariance(tmp_path):
 
 
 def test_bench_line_rates_are_their_own_legs():
-    """`python bench.py --steps 20 --warmup 5 --sustained 200` (what the driver runs): every rate in the line is the env-steps of
+    """`python bench.py --full --steps 20 --warmup 5 --sustained 200`: every rate in the line is the env-steps of
     ITS OWN timed block over that block's time — value, rollout_fused.value and sustained.value all satisfy
     rate * ms_per_step / 1e3 == envs (round 3 divided the cumulative counter of all legs by the last leg's time: 1.325x)."""
     import json
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "5", "--sustained", "200", "--no-cpu-baseline", "--configs", "off"],
+    run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "20", "--warmup", "5", "--sustained", "200", "--no-cpu-baseline", "--configs", "off"],
                          capture_output=True, text=True, timeout=500, cwd=root)
     assert run.returncode == 0, run.stderr[-3000:]
     line = json.loads([l for l in run.stdout.splitlines() if l.startswith("{")][-1])
@@ -1616,13 +1616,13 @@ def test_bench_line_rates_are_their_own_legs():
 
 
 def test_bench_line_carries_the_other_baseline_configs():
-    """The default command line (one rank, UnitreeA1.simple, 4096) also runs short legs of BASELINE configs 3-5 — HumanoidTorque.run 4096,
+    """The --full command line (one rank, UnitreeA1.simple, 4096) also runs short legs of BASELINE configs 3-5 — HumanoidTorque.run 4096,
     Atlas.walk with back joints + joint-damping randomisation 2048, HumanoidMuscle.run 2048 — under `configs`, each with its own kernel
     time, roofline, parity sample against the fp64 oracle and the replay kernel's share; nothing dropped anywhere."""
     import json
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "5", "--warmup", "2", "--sustained", "0", "--fuse", "0",
+    run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "5", "--warmup", "2", "--sustained", "0", "--fuse", "0",
                           "--no-cpu-baseline", "--config-steps", "10", "--config-warmup", "5"], capture_output=True, text=True, timeout=900, cwd=root)
     assert run.returncode == 0, run.stderr[-3000:]
     line = json.loads([l for l in run.stdout.splitlines() if l.startswith("{")][-1])
@@ -1639,6 +1639,36 @@ def test_bench_line_carries_the_other_baseline_configs():
         # beside `value`: the same rollout with 25 control steps per launch (no join behind every control step), nothing dropped either
         f = c["rollout_fused"]
         assert "error" not in f and f["steps_per_launch"] == 25 and f["overflow_contacts"] == 0 and abs(f["value"] * f["ms_per_step"] * 1e-3 / envs - 1.0) < 1e-9
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_its_outputs(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times exactly the K control steps (`ms_per_step` is that block's), runs none of
+    the --full legs, and with `--dump-outputs DIR` writes what the block computed; two runs with the same arguments write the same
+    states."""
+    import json
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines, dumps = [], []
+    for k in range(2):
+        out_dir = tmp_path / ("run%d" % k)
+        run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "5",
+                              "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=300, cwd=root)
+        assert run.returncode == 0, run.stderr[-3000:]
+        lines.append(json.loads([l for l in run.stdout.splitlines() if l.startswith("{")][-1]))
+        dumps.append({f[:-4]: np.load(str(out_dir / f)) for f in sorted(os.listdir(str(out_dir)))})
+    line = lines[0]
+    assert line["steps"] == line["timed_steps"] == line["burst"]["steps"] == 30 and line["warmup"] == 5
+    assert line["ms_per_step"] == line["burst"]["ms_per_step"] and abs(line["value"] * line["ms_per_step"] * 1e-3 / 4096 - 1.0) < 1e-9
+    assert line["unit"] == "env-steps/s" and line["higher_is_better"] is True and line["dtype"] == "f32" and "metric" in line
+    assert not {"sustained", "rollout_fused", "parity", "cpu_baseline", "python_surface", "configs"} & set(line), sorted(line)
+    d = dumps[0]
+    assert sorted(d) == ["flags", "qpos", "qvel", "stats"]
+    assert d["qpos"].shape == d["qvel"].shape == (4096, 18) and d["qpos"].dtype == np.float32 and d["flags"].shape == (4096,)
+    assert np.isfinite(d["qpos"]).all() and np.isfinite(d["qvel"]).all()
+    assert d["stats"].dtype == np.float64 and d["stats"][0] == 4096 * 30                # env_steps of the timed block
+    for name in ("qpos", "qvel", "flags"):
+        assert np.array_equal(d[name], dumps[1][name]), name
+    assert np.allclose(d["stats"], dumps[1]["stats"], rtol=1e-6, atol=0)
 
 
 @pytest.mark.parametrize("task", ["run", "walk"])

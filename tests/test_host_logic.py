@@ -743,6 +743,45 @@ def test_bench_leg_rate_identity_and_parity_flag():
     assert "lm_get_state after the timed block" in src and set(bench.PARITY_REPORTED_NOT_GATING) == {"UnitreeH1.walk", "UnitreeH1.run", "UnitreeH1.carry"}
 
 
+def test_bench_dump_outputs_names_dtypes_and_size_cap(tmp_path):
+    """`bench.py --dump-outputs DIR` (no GPU needed for the writer): float32 / float64 arrays named after what the timed path leaves
+    behind; above the 64 MB cap a fixed, sorted sample of environments with its global ids, the same sample every time."""
+    import importlib.util
+    import types
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    def fake(n, nv, na, offset=0):
+        rs = np.random.RandomState(1)
+        q, v, a = (rs.randn(n, k).astype(np.float32) for k in (nv, nv, max(na, 1)))
+        b = types.SimpleNamespace(na=na, get_state=lambda: (q, v), get_activation=lambda: a[:, :na],
+                                  flags=lambda: (np.arange(n) % 3).astype(np.uint8))
+        return types.SimpleNamespace(b=b, n=n, offset=offset), q
+    st = {k: float(i + 1) for i, k in enumerate(bench.DUMP_STATS)}
+    st["kernel_ms"] = 0.5
+    W, q = fake(64, 18, 0)
+    bench.dump_outputs(W, st, str(tmp_path / "small"), 0, 1)
+    d = {f[:-4]: np.load(str(tmp_path / "small" / f)) for f in os.listdir(str(tmp_path / "small"))}
+    assert sorted(d) == ["flags", "qpos", "qvel", "stats"]
+    assert np.array_equal(d["qpos"], q) and d["qpos"].dtype == np.float32 and d["flags"].dtype == np.float32
+    assert d["stats"].dtype == np.float64 and list(d["stats"]) == [st[k] for k in bench.DUMP_STATS]
+    # a batch whose arrays exceed the cap: a sample of environments, within the cap, reproducible
+    n = 160000
+    for run in ("big0", "big1"):
+        W, q = fake(n, 60, 40, offset=n)
+        bench.dump_outputs(W, st, str(tmp_path / run), 0, 1)
+    files = sorted(os.listdir(str(tmp_path / "big0")))
+    assert files == ["act.npy", "env_index.npy", "flags.npy", "qpos.npy", "qvel.npy", "stats.npy"]
+    assert sum(os.path.getsize(str(tmp_path / "big0" / f)) for f in files) <= 64 * 10 ** 6
+    idx = np.load(str(tmp_path / "big0" / "env_index.npy"))
+    assert idx.dtype == np.float64 and 0 < len(idx) < n and (np.diff(idx) > 0).all() and idx.min() >= n
+    assert np.array_equal(np.load(str(tmp_path / "big0" / "qpos.npy")), q[idx.astype(np.int64) - n])
+    for f in files:
+        assert np.array_equal(np.load(str(tmp_path / "big0" / f)), np.load(str(tmp_path / "big1" / f))), f
+
+
 def test_model_rule_randomisation_with_several_models(tmp_path):
     """Several models in one environment (the reference's MultiMuJoCo) TOGETHER with randomisation rules that change compile-time
     constants: one pool of model variants per model, for n_envs = 1 (one device batch per model, the model drawn per episode) and
