@@ -168,6 +168,7 @@ struct Params {
   int root_xyz;       // the root's translations are slides along +x, +y, +z in a root frame that is the world's (solve(): ROOT_XYZ)
   int root_limited;   // some root dof is `limited` (lowering.py keeps a root limit only when it can become active): the regular kernels of
                       // the families without root limit rows look at the root positions every pass (forward: ROOT_LIM)
+  int neq, off_eq;    // joint equality records (LM_EQ_SIZE floats each) at off_eq in cmg: read by the kernels with equality rows only (solve: EQ_ROWS)
 };
 
 struct Counters { int solver_iters; int overflow; int unhandled; int ncon; int ls_evals; int ls_capped; int it_max;
@@ -269,9 +270,9 @@ template <int MC, int NS, int NM = 0, bool PAIRS = false, bool COMPACT = false> 
   static constexpr bool kBig = NS > 8;
   static constexpr int kQCap = kBig ? 128 : ((MC >= 5) ? 24 : 8);    // convex pairs per chain and pass
   static constexpr int kRCap = kBig ? 64 : ((NS < 8) ? NS : 8);      // contacts per chain and pass
-  // (the six-link kernels compute the sphere centres from the link frames, like the detection-only ones: 18 floats per column that —
+  // (the six- and seven-link kernels compute the sphere centres from the link frames, like the detection-only ones: 18 floats per column that —
   // with their prune records and link groups read from the table's copy in global memory — put the family back at FOUR workgroups per CU)
-  static constexpr int kLists = kBS + ((PAIRS && MC != 6) ? MC * 3 : 0);
+  static constexpr int kLists = kBS + ((PAIRS && MC < 6) ? MC * 3 : 0);
   // the ROOT twists of the kernels that build their inertias behind the pair pass (forward: DEFER): the root is replicated in the four
   // chain lanes of an environment, so its 36 numbers are STRIPED over the four columns (element i in column i & 3, field i >> 2) —
   // 9 floats per column outside the part of lane memory the pair pass's work lists overlay, written before the pass
@@ -1822,7 +1823,7 @@ LM_DEV void forward(const float* cm, int c, const Params& P, float* qr, float* v
   constexpr bool DEFER = PAIRS && MC >= 5;        // (the quadruped's kernel — three links, no scratch — keeps its kinematics in one loop)
 #endif
   // the link-pair lists: in the constant table (LDS) — the six-link kernels' in its global copy (Params::cmg)
-#define LPE(off, i, f) ((MC == 6) ? P.cmg[(off) + (i) * LM_LP_SIZE + (f)] : cm[oz + (off) + (i) * LM_LP_SIZE + (f)])
+#define LPE(off, i, f) ((MC >= 6) ? P.cmg[(off) + (i) * LM_LP_SIZE + (f)] : cm[oz + (off) + (i) * LM_LP_SIZE + (f)])
 #ifdef LM_A1_CAPBOX_INLINE
   constexpr bool kCapBox = true;
 #else
@@ -1855,22 +1856,22 @@ LM_DEV void forward(const float* cm, int c, const Params& P, float* qr, float* v
   // the chain's tail lists (prune records, collider-less geoms, geom groups, link pairs): contiguous per chain, start in the chain block
 // (six-link kernels: the prune records and the link groups are read from the constant table's copy in GLOBAL memory, like their link-pair
 // lists — lowering.py ends H_CM_USED in front of them: 1.8 KB of LDS that decide between three and four workgroups per CU)
-#define GP(g, f) ((MC == 6) ? P.cmg[(int)CH(LM_C_OFF_PRUNE) + (g) * LM_P_SIZE + (f)] : cm[oz + (int)CH(LM_C_OFF_PRUNE) + (g) * LM_P_SIZE + (f)])
+#define GP(g, f) ((MC >= 6) ? P.cmg[(int)CH(LM_C_OFF_PRUNE) + (g) * LM_P_SIZE + (f)] : cm[oz + (int)CH(LM_C_OFF_PRUNE) + (g) * LM_P_SIZE + (f)])
 #define CU(i, f) cm[oz + (int)CH(LM_C_OFF_CUNSUP) + (i) * LM_U_SIZE + (f)]
 #define SL(s, f) lmem[((s) * LMm::kSlot + (f)) * ls]
 #define PEER(dl, i) Q::peer(lmem, ls, (i), (dl))
 #define DAMP_R(i) (DR ? dp->damp[(long long)(int)RD(i, LM_D_DOF) * dp->stride] : RD(i, LM_D_DAMP))
 #define STIFF_R(i) (DR ? dp->stiff[(long long)(int)RD(i, LM_D_DOF) * dp->stride] : RD(i, LM_D_STIFF))
 #define FLOSS_R(i) (DR ? dp->floss_r[i] : RD(i, LM_D_FLOSS))
-#define DUPK(k) (MC == 6 && duprole < 0 && (k) == 0)       /* the copy of a shared link carries no joint parameters */
+#define DUPK(k) (MC >= 6 && duprole < 0 && (k) == 0)       /* the copy of a shared link carries no joint parameters */
 #define DAMP_C(k) (DR ? (DUPK(k) ? 0.0f : dp->damp[(long long)(int)LK(k, LM_D_DOF) * dp->stride]) : LK(k, LM_D_DAMP))
 #define STIFF_C(k) (DR ? (DUPK(k) ? 0.0f : dp->stiff[(long long)(int)LK(k, LM_D_DOF) * dp->stride]) : LK(k, LM_D_STIFF))
 #define FLOSS_C(k) (DR ? (DUPK(k) ? 0.0f : dp->floss_c[k]) : LK(k, LM_D_FLOSS))
   const float w0 = (c == 0) ? 1.0f : 0.0f;    // root rows are replicated in all lanes, counted once
   const int nl = (int)CH(LM_C_NLINKS);
   // chains that share their first link (compiled for the six-link family only): +1 owner, -1 massless copy, see tie_shared_dof
-  const int duprole = (MC == 6) ? (int)CH(LM_C_DUPROLE) : 0;
-  const bool anydup = (MC == 6) && Q::sum(fabsf((float)duprole)) > 0.0f;
+  const int duprole = (MC >= 6) ? (int)CH(LM_C_DUPROLE) : 0;
+  const bool anydup = (MC >= 6) && Q::sum(fabsf((float)duprole)) > 0.0f;
   LM_TICK_INIT();
 
   // ================= position stage: kinematics, twists, inertias, contacts =================
@@ -2018,7 +2019,7 @@ LM_DEV void forward(const float* cm, int c, const Params& P, float* qr, float* v
             // self-collision broad phase: world centre of the link's bounding sphere, and the speed of the link's points
             // against the root body, |v_c| + |w| r with the twist relative to the root (the detection's travel bound)
             const V3 cw = pk + mul(Rk, v3(LX(k, LM_L_BSX), LX(k, LM_L_BSY), LX(k, LM_L_BSZ)));
-            if (PAIRS && MC != 6) { LMEM(LMm::kBS + k * 3 + 0) = cw.x; LMEM(LMm::kBS + k * 3 + 1) = cw.y; LMEM(LMm::kBS + k * 3 + 2) = cw.z; }      // (detection only: from the frames, bs_centre)
+            if (PAIRS && MC < 6) { LMEM(LMm::kBS + k * 3 + 0) = cw.x; LMEM(LMm::kBS + k * 3 + 1) = cw.y; LMEM(LMm::kBS + k * 3 + 2) = cw.z; }      // (detection only: from the frames, bs_centre)
             const V3 wr = V.w - Vroot.w;
             const V3 vcr = V.v - Vroot.v + cross(wr, cw - O);
             pair_speed = fmaxf(pair_speed, sqrtf(dot(vcr, vcr)) + sqrtf(dot(wr, wr)) * LX(k, LM_L_BSR));
@@ -2061,7 +2062,7 @@ LM_DEV void forward(const float* cm, int c, const Params& P, float* qr, float* v
       // a link high above the floor costs one test per pass
       const int ngroups = (int)CH(LM_C_NLGROUP), off_lgroup_c = (int)CH(LM_C_OFF_LGROUP);
       for (int gi = 0; gi < ngroups; gi++) {
-#define LG(f) ((MC == 6) ? P.cmg[off_lgroup_c + gi * LM_LG_SIZE + (f)] : cm[oz + off_lgroup_c + gi * LM_LG_SIZE + (f)])
+#define LG(f) ((MC >= 6) ? P.cmg[off_lgroup_c + gi * LM_LG_SIZE + (f)] : cm[oz + off_lgroup_c + gi * LM_LG_SIZE + (f)])
         const int glink = (int)LG(0), gfirst = (int)LG(1), gend = gfirst + (int)LG(2);
         {
           const int fbg = LMm::kFrame + (glink < 0 ? 0 : glink) * 18;
@@ -2574,13 +2575,13 @@ LM_DEV void forward(const float* cm, int c, const Params& P, float* qr, float* v
       // tests entries r, r + kRep, ... and keeps bit i / kRep of its mask for an entry in reach; the masks are exchanged
       // (exact as floats: <= 64 / kRep bits... 16 with four replicas), every replica then builds the same lists from them.
       // (six-link chains: up to 128 entries per lane, a second mask word)
-      constexpr bool kWide = MC == 6;
+      constexpr bool kWide = MC >= 6;
       constexpr int kEB = kWide ? 128 : 64;                          // an entry of W = entry index + kEB * its body pairs
       unsigned long long reach_r = 0ull, reach_r2 = 0ull;
       // world centre of a link's bounding sphere: kept in lane memory by the kernels with the full pair pass, from the link frame
       // otherwise (detection only: no room for it beside the six-link lane memory)
       auto bs_centre = [&](int dl, int lane, int k) -> V3 {
-        if constexpr (PAIRS && MC != 6) return v3(PEER(dl, LMm::kBS + k * 3), PEER(dl, LMm::kBS + k * 3 + 1), PEER(dl, LMm::kBS + k * 3 + 2));
+        if constexpr (PAIRS && MC < 6) return v3(PEER(dl, LMm::kBS + k * 3), PEER(dl, LMm::kBS + k * 3 + 1), PEER(dl, LMm::kBS + k * 3 + 2));
         else {
           const int fb = LMm::kFrame + k * 18;
           M3 Rl;
@@ -3094,7 +3095,7 @@ LM_DEV void forward(const float* cm, int c, const Params& P, float* qr, float* v
   // factorisation eliminates the lanes in order and carries the cross blocks along (arrow_factor_g): exact for any pattern.
   bool any_pair = false;
   int adj0 = 0;
-  constexpr int NX = PAIRS ? ((MC <= 3 || MC == 6) ? 3 : 2) : 1;         // cross blocks a lane may hold: chains above it (quadruped and six-link robots 4 chains, humanoids 3)
+  constexpr int NX = PAIRS ? ((MC <= 3 || MC == 6) ? 3 : 2) : 1;         // cross blocks a lane may hold: chains above it (quadruped and six-link robots 4 chains, humanoids 3 — the seven-link one too)
   if (PAIRS) {
     adj0 = (int)(Q::sum((float)(pair_mask_out << (4 * c))) + 0.5f);
     // symmetric closure (a lane that ran out of slots may lack its mirror of a contact its partner holds)
@@ -3166,6 +3167,29 @@ LM_DEV void forward(const float* cm, int c, const Params& P, float* qr, float* v
           lim_s_c[k] = sgn; lim_D_c[k] = 1.0f / Rl;
           lim_aref_c[k] = -LK(k, LM_D_LIM_B) * (sgn * vc[k]) - LK(k, LM_D_LIM_K) * imp * dist;
         }
+      }
+    }
+  }
+  // joint equality rows (MuJoCo 2.3.7 mj_instantiateEquality / mj_makeImpedance for `<equality><joint>` without joint2): pos = q - qpos0 -
+  // polycoef[0], J = the dof's unit row, imp from |pos|, R = (1 - imp) / imp * dof_invweight0, aref = -b v - k imp pos; always active: a
+  // two-sided quadratic row 1/2 (1/R) (a - aref)^2 on the link's dof, beside a limit row of the same joint. Compiled into the seven-link
+  // family only (the mesh-foot humanoid's subtalar / mtp constraints); lm_model_create refuses equality records for any other family.
+  constexpr bool EQ_ROWS = MC >= 7;
+  constexpr int NEQ = EQ_ROWS ? MC : 1;
+  float eq_D_c[NEQ], eq_aref_c[NEQ];      // eq_D_c = 0: no equality row on that link
+#pragma unroll
+  for (int k = 0; k < NEQ; k++) { eq_D_c[k] = 0; eq_aref_c[k] = 0; }
+  if constexpr (EQ_ROWS) {
+    for (int i = 0; i < P.neq; i++) {
+      const float* er = P.cmg + P.off_eq + i * LM_EQ_SIZE;
+      const int lane = (int)er[LM_EQ_LANE], link = (int)er[LM_EQ_LINK];
+#pragma unroll
+      for (int k = 0; k < MC; k++) if (lane == c && link == k && k < nl) {
+        const float pos = qc[k] - er[LM_EQ_REF];
+        const float imp = impedance(er + LM_EQ_S0, 1, pos, 0.0f);
+        const float Re = fmaxf(kMinVal, (1.0f - imp) * LKV(k, 1, LM_D_INVW) / imp);
+        eq_D_c[k] = 1.0f / Re;
+        eq_aref_c[k] = -er[LM_EQ_B] * vc[k] - er[LM_EQ_K] * imp * pos;
       }
     }
   }
@@ -3269,6 +3293,7 @@ LM_DEV void forward(const float* cm, int c, const Params& P, float* qr, float* v
         cost += friction_cost(xc[k] - fl_aref_c[k], FLOSS_C(k), (inr_on ? dp->rfl_c[k] : LK(k, LM_D_FLOSS_R)));
         float x = lim_s_c[k] * xc[k] - lim_aref_c[k];
         if (lim_s_c[k] != 0.0f && x < 0.0f) cost += 0.5f * lim_D_c[k] * x * x;
+        if constexpr (EQ_ROWS) { const float xe = xc[k] - eq_aref_c[k]; cost += 0.5f * eq_D_c[k] * xe * xe; }
       }
     }
     if (nslot > 0 || any_pair) {
@@ -3357,7 +3382,7 @@ LM_DEV void forward(const float* cm, int c, const Params& P, float* qr, float* v
 #pragma unroll
   for (int i = 0; i < 6; i++) has_rows = has_rows || (FLOSS_R(i) > 0.0f) || (ROOT_LIM && lim_s_r[ROOT_LIM ? i : 0] != 0.0f);
 #pragma unroll
-  for (int k = 0; k < MC; k++) has_rows = has_rows || (k < nl && (FLOSS_C(k) > 0.0f || lim_s_c[k] != 0.0f));
+  for (int k = 0; k < MC; k++) has_rows = has_rows || (k < nl && (FLOSS_C(k) > 0.0f || lim_s_c[k] != 0.0f || (EQ_ROWS && eq_D_c[EQ_ROWS ? k : 0] != 0.0f)));
   has_rows = has_rows || nslot > 0;
   bool done = !(Q::sum(has_rows ? 1.0f : 0.0f) > 0.0f);   // quad-uniform: nothing to solve in this environment
   int iters = 0;
@@ -3368,7 +3393,7 @@ LM_DEV void forward(const float* cm, int c, const Params& P, float* qr, float* v
     oz = LM_OPAQUE_ZERO();
     if (!done) {
       // ---- gradient at the current point
-      float jfr_r[6], jfr_c[MC], jlim_c[MC];     // jar of the unit rows
+      float jfr_r[6], jfr_c[MC], jlim_c[MC], jeq_c[NEQ];     // jar of the unit rows
       if (kMaIncr && it > 0) {}
       else if (!(P.ablate & 16)) mulM(ar, ac, Mar, Mac);
       else {
@@ -3404,6 +3429,7 @@ LM_DEV void forward(const float* cm, int c, const Params& P, float* qr, float* v
         float fu = -fminf(fmaxf(jfr_c[k] * iR_c[k], -ff_c[k]), ff_c[k]);
         if (fabsf(jfr_c[k]) < Rr * ff_c[k]) act_fr_c |= 1u << k;
         if (jlim_c[k] < 0.0f && lim_s_c[k] != 0.0f) { fu -= lim_s_c[k] * lim_D_c[k] * jlim_c[k]; act_lim |= 1u << k; }
+        if constexpr (EQ_ROWS) { jeq_c[k] = ac[k] - eq_aref_c[k]; fu -= eq_D_c[k] * jeq_c[k]; }
         qf_c[k] = fu;
       }
       Sp Fl[MC];                 // contact wrench sums per link
@@ -3550,6 +3576,7 @@ LM_DEV void forward(const float* cm, int c, const Params& P, float* qr, float* v
           for (int r = 0; r < 6; r++) Hcr[k][r] = own * LMEM(LMm::kMcr + k * 6 + r);
           if (act_fr_c & (1u << k)) Hcc[tri(k, k)] += own * iR_c[k];
           if (act_lim & (1u << k)) Hcc[tri(k, k)] += own * lim_D_c[k];
+          if constexpr (EQ_ROWS) Hcc[tri(k, k)] += own * eq_D_c[k];
         }
 #pragma unroll
         for (int i = 0; i < 21; i++) Hpart[i] = 0;
@@ -3856,6 +3883,10 @@ LM_DEV void forward(const float* cm, int c, const Params& P, float* qr, float* v
               const float xl = fminf(fmaf(alpha, jvlim_c[k], jlim_c[k]), 0.0f);       // lim_D_c = 0 when no limit is active
               t = fmaf(lim_D_c[k] * xl, jvlim_c[k], t);
               a2 = fmaf((xl < 0.0f) ? lim_D_c[k] : 0.0f, jvlim_c[k] * jvlim_c[k], a2);
+              if constexpr (EQ_ROWS) {
+                t = fmaf(eq_D_c[k] * fmaf(alpha, jv_c[k], jeq_c[k]), jv_c[k], t);
+                a2 = fmaf(eq_D_c[k], jv_c[k] * jv_c[k], a2);
+              }
               a1 += t; am += fabsf(t);
 #ifdef LM_LS_TRACE
               if (getenv("LM_ROWS")) printf("      lane %d row %d alpha %.6g t %.6g x %.5g iR %.4g f %.3g limD %.4g xl %.5g\n", c, k, alpha, t, x, iR_c[k], ff_c[k], lim_D_c[k], xl);

@@ -1,5 +1,5 @@
 // lm_family.hip — one kernel family (LM_FAMILY) and part (LM_PART) of the step kernels; see lm_step.h.
-// The library links one object per family and part (parts 0..2 of the families 0, 2, 4, 5 and 7..10, parts 0..1 of the generic family 6) so that `make -j`
+// The library links one object per family and part (parts 0..2 of the families 0, 2, 4, 5 and 7..11, parts 0..1 of the generic family 6) so that `make -j`
 // builds them in parallel.
 #include "lm_step.h"
 
@@ -43,6 +43,8 @@ bool LM_CAT(launch_f, LM_FAMILY, p, LM_PART)(const LaunchCtx& L, const KArgs& a,
   return launch_family<5, 8, false, LM_CONE_PYRAMIDAL, 0, LM_PART, 1>(L, a, kind);
 #elif LM_FAMILY == 10   // HumanoidMuscle with its bone hulls colliding
   return launch_family<5, 8, false, LM_CONE_PYRAMIDAL, LM_MAXMUS, LM_PART, 1>(L, a, kind);
+#elif LM_FAMILY == 11   // HumanoidTorque with mesh feet (seven-link legs: subtalar, mtp), its bone hulls colliding, joint equality rows (RK4)
+  return launch_family<7, 8, true, LM_CONE_PYRAMIDAL, 0, LM_PART, 1>(L, a, kind);
 #elif LM_PART == 2
   return false;          // the generic family has no kernels with per-environment parameters
 #else

@@ -94,6 +94,8 @@ static int family_of(const lm_batch* b) {
   const bool big = T.max_links > 3, six = T.max_links > 5, rk4 = b->m->P.integrator == LM_INT_RK4, few = T.max_contacts <= 4;
   static const bool generic = LM_PROBE_ENV("LM_GENERIC_KERNELS") != nullptr;      // A/B: run-time cone for the humanoids
   const bool pyr3 = T.all_pyr3 && !generic;
+  // seven-link chains (the mesh-foot humanoid): RK4, condim-3 pyramids, no muscles, the pair pass and the joint equality rows
+  if (T.max_links > 6) return (rk4 && T.na == 0 && pyr3) ? 11 : -1;
   if (six) return (!rk4 && T.na == 0 && pyr3) ? 7 : -1;      // (with or without self-collision tables: its regular kernels detect, its replay kernel collides)
   // five-link humanoids whose lowering carries self-collision tables (bone hulls, link meshes, cylinders): the pair families
   if (big && T.npair > 0 && pyr3) return rk4 ? (T.na == 0 ? 8 : 6) : (T.na == 0 ? 9 : 10);
@@ -108,7 +110,8 @@ static int family_of(const lm_batch* b) {
 }
 
 static bool family_has_replicas(const lm_batch* b) { return family_of(b) != 6; }
-static bool family_has_pairs(int fam) { return fam == 0 || fam == 7 || fam == 8 || fam == 9 || fam == 10; }
+static bool family_has_pairs(int fam) { return fam == 0 || fam == 7 || fam == 8 || fam == 9 || fam == 10 || fam == 11; }
+static bool family_has_equality_rows(int fam) { return fam == 11; }
 
 // (Round 5, tried and dropped: a one-workgroup GATE kernel in front of the regular launch that waits until the launch's pollers are
 // resident, and a higher priority for their stream. Launched first on their own stream the pollers lose the race for the chip in 7
@@ -125,9 +128,9 @@ static void launch_variant(lm_batch* b, const KArgs& a) {
       {lmk::launch_f4p0, lmk::launch_f4p1, lmk::launch_f4p2}, {lmk::launch_f5p0, lmk::launch_f5p1, lmk::launch_f5p2},
       {lmk::launch_f6p0, lmk::launch_f6p1, lmk::launch_f6p2}, {lmk::launch_f7p0, lmk::launch_f7p1, lmk::launch_f7p2},
       {lmk::launch_f8p0, lmk::launch_f8p1, lmk::launch_f8p2}, {lmk::launch_f9p0, lmk::launch_f9p1, lmk::launch_f9p2},
-      {lmk::launch_f10p0, lmk::launch_f10p1, lmk::launch_f10p2}};
+      {lmk::launch_f10p0, lmk::launch_f10p1, lmk::launch_f10p2}, {lmk::launch_f11p0, lmk::launch_f11p1, lmk::launch_f11p2}};
   const int fam = family_of(b);
-  if (fam < 0) { g_launch_err = "chains of six links are compiled for Euler, condim-3 pyramids, no muscles only"; return; }
+  if (fam < 0) { g_launch_err = "chains of six links are compiled for Euler, of seven links for RK4 — condim-3 pyramids, no muscles only"; return; }
   const LaunchCtx L = {b->stream, b->n_active, b->epb};
   if (b->n_active <= 0) return;            // an empty active list: nothing to run
   if (fam == 6) {
@@ -223,7 +226,7 @@ int lm_model_create(const double* cmod, size_t n, int device, lm_model** out) {
   if (!cmod || n < LM_HEADER_SIZE + LM_CM_SIZE + LM_GT_SIZE) return fail("chain model too short");
   if ((unsigned)cmod[LM_H_MAGIC] != (unsigned)LM_LMC_MAGIC) return fail("bad chain-model magic");
   if ((int)cmod[LM_H_CM_SIZE] != LM_CM_SIZE || (int)cmod[LM_H_GT_SIZE] != LM_GT_SIZE) return fail("chain-model table size mismatch (regenerate include/lm_layout.h)");
-  if ((int)cmod[LM_H_MAXLINKS] > LM_MAXC) return fail("chains longer than 6 links are not supported");
+  if ((int)cmod[LM_H_MAXLINKS] > LM_MAXC) return fail("chains longer than 7 links are not supported");
   if ((int)cmod[LM_HEADER_SIZE + LM_R_NDOF] != 6) return fail("root body must have 6 dofs");
   const int n_muscle = (int)cmod[LM_H_NMUSCLE];
   if (n_muscle < 0 || n_muscle > LM_MT_MAXMUS) return fail("bad muscle count");
@@ -356,6 +359,13 @@ int lm_model_create(const double* cmod, size_t n, int device, lm_model** out) {
   P.ls_tol = 1e-2f; P.ls_iters = 12; P.ls_noise = 2e-6f; P.ablate = 0;
   P.root_limited = m->root_limited ? 1 : 0;
   P.root_xyz = m->root_xyz ? 1 : 0;
+  P.neq = (int)cmod[LM_H_NEQ]; P.off_eq = (int)cmod[LM_H_OFF_EQ];
+  if (P.neq < 0 || (P.neq > 0 && (P.off_eq <= 0 || P.off_eq + P.neq * LM_EQ_SIZE > LM_CM_SIZE))) return fail("bad equality-record table");
+  for (int i = 0; i < P.neq; i++) {
+    const float* r = cm.data() + P.off_eq + i * LM_EQ_SIZE;
+    const int lane = (int)r[LM_EQ_LANE], link = (int)r[LM_EQ_LINK];
+    if (lane < 0 || lane >= LM_NCHAIN || link < 0 || link >= (int)cm[LM_CM_CHAINS + LM_C_NLINKS * LM_NCHAIN + lane]) return fail("equality record outside the chains");
+  }
   P.ls_grid[0] = 0.25f; P.ls_grid[1] = 0.0625f; P.ls_grid[2] = 0.015625f;
   if (const char* v = LM_PROBE_ENV("LM_LS_GRID")) sscanf(v, "%f,%f,%f", &P.ls_grid[0], &P.ls_grid[1], &P.ls_grid[2]);   // A/B knob
   if (const char* v = LM_PROBE_ENV("LM_LS_NOISE")) P.ls_noise = (float)atof(v);
@@ -454,6 +464,11 @@ int lm_batch_create(lm_model* m, int n_envs, lm_batch** out) {
     if (m->T.npair > 0 && !family_has_pairs(fam)) {
       delete b;
       return fail("the model carries self-collision tables but its kernel family has no pair pass (RK4 with muscles, or a cone / condim the pair families are not compiled for)");
+    }
+    // the same for joint equality rows: compiled into the seven-link family only (lm_core.h EQ_ROWS)
+    if (m->P.neq > 0 && !family_has_equality_rows(fam)) {
+      delete b;
+      return fail("the model carries joint equality rows but its kernel family has none (they are compiled into the seven-link family only)");
     }
   }
   if (batch_alloc(b)) { lm_batch_destroy(b); return 1; }     // g_err holds the failed call; nothing leaks

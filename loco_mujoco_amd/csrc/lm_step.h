@@ -673,7 +673,7 @@ __global__ __launch_bounds__(64) void step_kernel(KArgs a) {
       const int o0 = (int)cm[LM_CM_CHAINS + LM_C_GRF_OBS0 * LM_NCHAIN + c], o1 = (int)cm[LM_CM_CHAINS + LM_C_GRF_OBS1 * LM_NCHAIN + c];
 #pragma unroll
       for (int j = 0; j < 3; j++) { if (o0 >= 0) o[o0 + j] = cnt.grf[0][j] * scale; if (o1 >= 0) o[o1 + j] = cnt.grf[1][j] * scale; }
-      if (MC == 6) {          // UnitreeG1: four force points per foot
+      if (MC >= 6) {          // UnitreeG1: four force points per foot
         const int o2 = (int)cm[LM_CM_CHAINS + LM_C_GRF_OBS2 * LM_NCHAIN + c], o3 = (int)cm[LM_CM_CHAINS + LM_C_GRF_OBS3 * LM_NCHAIN + c];
 #pragma unroll
         for (int j = 0; j < 3; j++) { if (o2 >= 0) o[o2 + j] = cnt.grf[2][j] * scale; if (o3 >= 0) o[o3 + j] = cnt.grf[3][j] * scale; }
@@ -761,8 +761,9 @@ struct LaunchCtx { hipStream_t stream; int N, epb; };
 // kernel kinds of one family (picked by the host, lm_kernels.hip::launch_variant)
 enum { LMK_FWD = 0, LMK_REP4, LMK_REP1, LMK_DR_REP4, LMK_DR_REP1, LMK_FUSED, LMK_FUSED_DR, LMK_DRV_REP4, LMK_DRV_REP1, LMK_FUSED_DRV,
        LMK_BIG, LMK_BIG_DR, LMK_BIG_DRV /* the replay kernels, one per part */, LMK_NKINDS };
-constexpr int LMK_NFAMILY = 11;     // 0 quadruped, 2 humanoid RK4 8 slots, 4 Euler 8 slots, 5 muscles, 6 generic, 7 six-link chains (Euler, 8 slots), (1 / 3: the four-slot humanoid families, dropped in round 5)
+constexpr int LMK_NFAMILY = 12;     // 0 quadruped, 2 humanoid RK4 8 slots, 4 Euler 8 slots, 5 muscles, 6 generic, 7 six-link chains (Euler, 8 slots), (1 / 3: the four-slot humanoid families, dropped in round 5)
                                     // 8 / 9 / 10 = five-link humanoids WITH self-collisions (8 slots): RK4 | Euler | Euler + muscles
+                                    // 11 = seven-link chains WITH self-collisions and joint equality rows (RK4, 8 slots): the mesh-foot humanoid
 // Replicas of the replay kernels' ONE environment per workgroup. 4 (shipped): the regular kernels' arithmetic exactly — a control step
 // comes out bitwise the same from either kernel. 16 (-DLM_REPLAY_REP=16): the whole wave for the environment, everything that is dealt
 // over replicas / lanes dealt four times wider. Measured in round 5 (profiles/r5_notes.md §3): a hard HumanoidTorque costs 10.4 ms with
@@ -838,5 +839,6 @@ bool launch_f7p0(const LaunchCtx&, const KArgs&, int); bool launch_f7p1(const La
 bool launch_f8p0(const LaunchCtx&, const KArgs&, int); bool launch_f8p1(const LaunchCtx&, const KArgs&, int); bool launch_f8p2(const LaunchCtx&, const KArgs&, int);
 bool launch_f9p0(const LaunchCtx&, const KArgs&, int); bool launch_f9p1(const LaunchCtx&, const KArgs&, int); bool launch_f9p2(const LaunchCtx&, const KArgs&, int);
 bool launch_f10p0(const LaunchCtx&, const KArgs&, int); bool launch_f10p1(const LaunchCtx&, const KArgs&, int); bool launch_f10p2(const LaunchCtx&, const KArgs&, int);
+bool launch_f11p0(const LaunchCtx&, const KArgs&, int); bool launch_f11p1(const LaunchCtx&, const KArgs&, int); bool launch_f11p2(const LaunchCtx&, const KArgs&, int);
 
 }  // namespace lmk

@@ -48,14 +48,18 @@ class BaseHumanoid(LocoEnv):
     """Common part of the humanoid family (reference ``base_humanoid.py:14``)."""
 
     def __init__(self, use_muscles=False, use_box_feet=True, disable_arms=True, alpha_box_feet=0.5, xml_path=None,
-                 timestep=0.001, **kwargs):
-        if not use_box_feet or not disable_arms:
-            # use_box_feet=False keeps the subtalar / mtp joints (seven-joint legs) AND their joint equality constraints
-            # (humanoid_torque.xml `<equality>`: *_constraint), disable_arms=False adds two seven-joint arms that branch off the torso
-            # behind the three lumbar joints, with wrist equality constraints: chains of seven links, equality rows and a branch behind a
-            # three-dof chain are not built (DESIGN.md §7)
-            raise NotImplementedError("only the default humanoid configuration (box feet, arms disabled) is built: mesh feet / free arms "
-                                      "need seven-link chains, joint equality constraints and a branch behind the lumbar chain")
+                 timestep=0.001, model_path=None, **kwargs):
+        if not disable_arms:
+            # disable_arms=False adds two seven-joint arms that branch off the torso behind the three lumbar joints, with wrist equality
+            # constraints: a branch behind a three-dof chain is not built (DESIGN.md §7)
+            raise NotImplementedError("disable_arms=False is not built: the free arms branch off behind the three-joint lumbar chain")
+        if not use_box_feet and use_muscles:
+            raise NotImplementedError("HumanoidMuscle with mesh feet (use_box_feet=False) is not built")
+        if not use_box_feet and xml_path is None and model_path is None:
+            # mesh feet: the subtalar / mtp joints stay (seven-joint legs) with their joint equality constraints, and the feet collide
+            # as the bone meshes' convex hulls — which needs the mesh files: no compiled model of this configuration ships
+            raise NotImplementedError("HumanoidTorque with mesh feet (use_box_feet=False) needs its model: xml_path= (the reference's "
+                                      "humanoid_torque.xml, with its meshes) or model_path= (a .model.npz written by CompiledModel.save)")
         self._use_muscles, self._use_box_feet, self._disable_arms = use_muscles, use_box_feet, disable_arms
         joints_to_remove, motors_to_remove, equ_constr_to_remove, collision_groups = self._get_xml_modifications()
         drop = ["q_" + j for j in joints_to_remove] + ["dq_" + j for j in joints_to_remove]
@@ -64,6 +68,11 @@ class BaseHumanoid(LocoEnv):
         if xml_path is not None:
             handle = mjcf.MjcfHandle.from_path(xml_path)
             model = self._compile(handle, timestep, joints_to_remove, motors_to_remove, equ_constr_to_remove, alpha_box_feet)
+        elif model_path is not None:
+            model = mjcf.CompiledModel.load(model_path)
+            assert abs(model.timestep - timestep) < 1e-12
+            missing = [j for j in _LEG if (j + "_r") not in model.jnt_names]
+            assert use_box_feet == bool(missing), "model_path: the model's legs do not match use_box_feet=%s" % use_box_feet
         else:
             model = mjcf.CompiledModel.load(_PKG / "assets" / self._asset_name())
             assert abs(model.timestep - timestep) < 1e-12
@@ -75,13 +84,15 @@ class BaseHumanoid(LocoEnv):
     def _compile(self, handle, timestep, joints_to_remove, motors_to_remove, equ_constr_to_remove, alpha_box_feet=0.5):
         """The reference's constructor-time XML surgery (``base_humanoid.py:49-64``), then the mini-compiler."""
         self._delete_from_xml_handle(handle, joints_to_remove, motors_to_remove, equ_constr_to_remove)
-        self._add_box_feet_to_xml_handle(handle, alpha_box_feet)
+        if self._use_box_feet:
+            self._add_box_feet_to_xml_handle(handle, alpha_box_feet)
         self._reorient_arms(handle)
         return mjcf.compile_mjcf(handle, timestep=timestep, drop_mesh_geoms=True)
 
     @staticmethod
     def _delete_from_xml_handle(xml_handle, joints_to_remove, motors_to_remove, equ_constraints):
-        """Remove joints / motors / equality constraints by name (reference ``base.py:865-890``)."""
+        """Remove joints / motors / equality constraints by name (reference ``base.py:865-890``). The active equality constraints that
+        remain (the mesh-foot model's subtalar / mtp constraints) are compiled (``mjcf``) and lowered as equality rows."""
         for j in joints_to_remove:
             assert xml_handle.remove(xml_handle.find("joint", j)), j
         for mname in motors_to_remove:
@@ -91,8 +102,6 @@ class BaseHumanoid(LocoEnv):
             for el in list(eq):
                 if el.get("name") in equ_constraints:
                     eq.remove(el)
-            remaining = [el.get("name") for el in eq if el.get("active", "true") != "false"]
-            assert not remaining, "equality constraints are not simulated: %s" % remaining
         return xml_handle
 
     @staticmethod
@@ -281,6 +290,8 @@ class BaseHumanoid4Ages(BaseHumanoid):
 
     def __init__(self, scaling=None, scaling_trajectory_map=None, use_muscles=False, use_box_feet=True,
                  disable_arms=True, alpha_box_feet=0.5, xml_path=None, timestep=0.001, **kwargs):
+        if not use_box_feet:
+            raise NotImplementedError("the 4Ages humanoids with mesh feet (use_box_feet=False) are not built")
         scalings = self._default_scalings if scaling is None else (list(scaling) if isinstance(scaling, (list, tuple)) else [scaling])
         self._scalings = scalings
         self._scaling_trajectory_map = scaling_trajectory_map

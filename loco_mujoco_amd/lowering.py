@@ -27,7 +27,7 @@ import numpy as np
 
 from . import mjcf
 
-MAXC = 6          # links per chain the table has room for (5 for every robot but UnitreeG1's legs)
+MAXC = 7          # links per chain the table has room for (5 for most robots, 6 for UnitreeG1's legs, 7 for the mesh-foot humanoid's legs)
 NCHAIN = 4
 NROOT = 6
 MAXG = 68         # floor-collidable geoms per chain (with / without a device collider, each); the humanoid's trunk chain with its welded arms has 65 (every hand bone)
@@ -98,7 +98,12 @@ GPAIR_SIZE = GP_X2 + GX_SIZE
 # bounding capsule (centre, axis, half length, radius in the link frames; "1" = the pair's first link), the geom pairs between the
 # two bodies [BP_FIRST, BP_FIRST + BP_N) (<= 24) and their largest margin. A link pair's entry points at its body pairs
 (BP_P1, BP_A1, BP_H1, BP_R1, BP_P2, BP_A2, BP_H2, BP_R2, BP_FIRST, BP_N, BP_MARGIN, BP_SIZE) = (0, 3, 6, 7, 8, 11, 14, 15, 16, 17, 18, 20)
-CM_SIZE = ROOT_SIZE + CHAIN_SIZE * NCHAIN + MAXRG * U_SIZE + MAXG * (U_SIZE + P_SIZE) * NCHAIN + MAXLG * LG_SIZE * NCHAIN + MAXLP * LP_SIZE * NCHAIN
+# ---- joint equality rows (MuJoCo's `<equality><joint>` with joint1 only: pos = q - qpos0 - polycoef[0], J = the dof's unit row), a
+# tail list of the constant table that only models with such rows have (H_NEQ records at H_OFF_EQ, read from the table's copy in
+# global memory): lane, link, reference qpos0 + polycoef[0], stiffness / damping from solref, solimp, dof_invweight0
+(EQ_LANE, EQ_LINK, EQ_REF, EQ_K, EQ_B, EQ_S0, EQ_S1, EQ_S2, EQ_S3, EQ_S4, EQ_INVW, EQ_SIZE) = range(12)
+MAXEQ = 8
+CM_SIZE = ROOT_SIZE + CHAIN_SIZE * NCHAIN + MAXRG * U_SIZE + MAXG * (U_SIZE + P_SIZE) * NCHAIN + MAXLG * LG_SIZE * NCHAIN + MAXLP * LP_SIZE * NCHAIN + MAXEQ * EQ_SIZE
 # ---- the geom table (global memory, read when a geom's bounding sphere reaches the floor): full records interleaved
 # [geom][field][chain]
 GT_SIZE = MAXG * G_SIZE * NCHAIN
@@ -183,6 +188,7 @@ H_OFF_RUNSUP, H_OFF_CUNSUP, H_OFF_PRUNE, H_GT_SIZE, H_OFF_LPAIR, H_NGPAIR, H_OFF
 H_NMESHN, H_OFF_MESHN = 44, 45     # neighbour table of the hull vertices (floats: hull-local indices, -1 ends a vertex's list)
 H_NBPAIR, H_OFF_BPT = 46, 47       # body-pair table of the self-collision mid phase (BP_SIZE floats per record)
 H_NMESHADJ, H_OFF_MESHADJ = 48, 49  # adjacency blocks of the hull vertices (4 floats per entry): convex-pair collider
+H_NEQ, H_OFF_EQ = 50, 51            # joint equality records (EQ_SIZE floats each; both 0 for a model without equality rows)
 # H_NGPAIR geom-pair records start H_OFF_GPT floats into the chain-model array (behind the geom table and the muscle table)
 # H_OFF_*: offsets (floats from the start of the constant table) of the tail lists, see CM_SIZE
 # H_ACTMODE: 0 = joint motors (torque = gear * ctrl), 1 = position servos on every actuated joint
@@ -653,7 +659,7 @@ def lower(m, task):
     if shared_first:
         # a first link shared by two chains (tie_shared_dof) is compiled in the six-link kernels only: a robot with shorter chains
         # (UnitreeH1 with its torso joint and free arms: 1 + 4 links) runs there with an idle link slot per chain
-        max_links = MAXC
+        max_links = max(max_links, 6)
 
     # ---- muscles: every tendon must run over the root body and ONE chain, so that lane c owns it
     mt = None
@@ -787,7 +793,10 @@ def lower(m, task):
                      or (m.cone == mjcf.CONE_PYRAMIDAL and 3 < max_links <= 5 and not shared_first)
                      # six-link chains (UnitreeG1, UnitreeH1 with its arms): the regular kernels only DETECT (a geom pair within reach
                      # hands the control step to the family's replay kernel, which has the pair pass: csrc/lm_family.hip)
-                     or (m.cone == mjcf.CONE_PYRAMIDAL and max_links == 6 and m.integrator == mjcf.INT_EULER and not muscles)))
+                     or (m.cone == mjcf.CONE_PYRAMIDAL and max_links == 6 and m.integrator == mjcf.INT_EULER and not muscles)
+                     # seven-link chains (the mesh-foot humanoid, RK4): the whole pair pass, like the five-link HumanoidTorque family
+                     or (m.cone == mjcf.CONE_PYRAMIDAL and max_links == 7 and m.integrator == mjcf.INT_RK4 and not muscles
+                         and not shared_first)))
     pair_tab = _self_collision_tables(m, root, chains, kin, register_hull, hull_block, prov["pairs"]) if pairs_on else None
     h[H_OFF_LPAIR] = off
     off_before_lp = off
@@ -807,6 +816,14 @@ def lower(m, task):
         if m.cone == mjcf.CONE_PYRAMIDAL:
             max_contacts = 8                  # the pair families are compiled with eight slots per chain (floor + self-contacts)
             h[H_MAXCONTACTS] = max_contacts
+    eq_rows = _equality_records(m, prov["dofs"])
+    if eq_rows:
+        # (a model without equality rows keeps H_NEQ = H_OFF_EQ = 0 and its table exactly as before)
+        h[H_NEQ], h[H_OFF_EQ] = len(eq_rows), off
+        for i, r in enumerate(eq_rows):
+            cm[off + i * EQ_SIZE:off + (i + 1) * EQ_SIZE] = r
+        off += len(eq_rows) * EQ_SIZE
+        info["equality_rows"] = len(eq_rows)
     assert off <= CM_SIZE
     # what a workgroup copies into its LDS: everything — but the six-link kernels read their link-pair lists (3 KB for UnitreeG1) and, since
     # the end of round 6, their prune records and link groups (1.8 KB) from the table's copy in global memory: with them in LDS the family
@@ -814,7 +831,7 @@ def lower(m, task):
     h[H_CM_USED] = h[H_OFF_PRUNE] if max_links > 5 else off
     h[H_GT_SIZE] = GT_SIZE
     h[H_NGRF] = n_grf
-    if max_groups_seen > 2 and max_links < MAXC:
+    if max_groups_seen > 2 and max_links < 6:
         raise UnsupportedModel("more than two foot-force groups on one chain (four are compiled in the six-link kernels only)")
     if n_grf and sum(1 for c in range(len(chains)) for k in C_GRF_OBS if cm[CM_CHAINS + k * NCHAIN + c] >= 0) != len(grf_groups):
         raise UnsupportedModel("a foot-force group has no geom with a device collider")
@@ -837,6 +854,35 @@ def lower(m, task):
     info["mesh_vertices"] = len(mesh_verts)
     return np.concatenate([h, cm, gt] + ([mt] if mt is not None else []) + [gpt, meshv.ravel(), np.array(mesh_nbr, dtype=np.float64), bpt,
                                                                            np.array(mesh_adj, dtype=np.float64).ravel()]), info
+
+
+def _equality_records(m, dof_links):
+    """EQ_SIZE-float records of the model's active joint equalities (``mjcf._compile_equality``); raises for what the device lacks."""
+    n = len(getattr(m, "eq_type", ()))
+    if n == 0:
+        return []
+    where = {d: (c, li) for c, li, d, copy in dof_links if c >= 0 and not copy}
+    rows = []
+    for i in range(n):
+        name = m.eq_names[i] if i < len(m.eq_names) else str(i)
+        if m.eq_type[i] != mjcf.EQ_JOINT:
+            raise UnsupportedModel("equality %s: active connect / weld constraints are not built on the device" % name)
+        if m.eq_obj2id[i] >= 0:
+            raise UnsupportedModel("equality %s: a joint equality coupling two joints (joint2) is not built on the device" % name)
+        d = int(m.eq_obj1id[i])
+        if d not in where:
+            raise UnsupportedModel("equality %s: a joint equality on a root dof is not built on the device" % name)
+        c, li = where[d]
+        r = np.zeros(EQ_SIZE)
+        r[EQ_LANE], r[EQ_LINK] = c, li
+        r[EQ_REF] = 0.0 + m.eq_data[i, 0]                  # qpos0 of a hinge / slide is 0 (mjcf: ref = 0 is asserted)
+        r[EQ_K], r[EQ_B] = _kb(m.eq_solref[i], m.eq_solimp[i], m.timestep)
+        r[EQ_S0:EQ_S0 + 5] = _clip_solimp(m.eq_solimp[i])
+        r[EQ_INVW] = m.dof_invweight0[d]
+        rows.append(r)
+    if len(rows) > MAXEQ:
+        raise UnsupportedModel("more than %d joint equality constraints" % MAXEQ)
+    return rows
 
 
 # ---- model variants (inertial / armature / geom-friction randomisation): what differs between two lowerings of the same robot

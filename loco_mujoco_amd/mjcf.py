@@ -174,11 +174,12 @@ class CompiledModel:
     act_names: list = field(default_factory=list)
     site_names: list = field(default_factory=list)
     tendon_names: list = field(default_factory=list)
+    eq_names: list = field(default_factory=list)
     # arrays are attached dynamically (see compile_mjcf)
 
     _SCALARS = ("timestep", "cone", "impratio", "integrator", "iterations", "tolerance", "nbody", "njnt", "nv",
                 "ngeom", "nu", "na", "nsite", "ntendon", "meaninertia", "n_dropped_mesh_geoms")
-    _NAMES = ("body_names", "jnt_names", "geom_names", "act_names", "site_names", "tendon_names")
+    _NAMES = ("body_names", "jnt_names", "geom_names", "act_names", "site_names", "tendon_names", "eq_names")
 
     def save(self, path):
         """Serialise to an ``.npz`` (arrays + a JSON header); see :meth:`load`."""
@@ -809,9 +810,52 @@ def compile_mjcf(handle, timestep=None, drop_mesh_geoms=False):
     m.act_biasprm = np.array([a["biasprm"] for a in acts]).reshape(-1, 3)
     m.act_forcerange = np.array([a["forcerange"] for a in acts]).reshape(-1, 2)
     m.act_forcelimited = np.array([a["forcelimited"] for a in acts], dtype=np.int32)
+    _compile_equality(m, root, defaults)
 
     _set_const(m)
     return m
+
+
+EQ_CONNECT, EQ_WELD, EQ_JOINT = 0, 1, 2
+_EQ_TYPES = {"connect": EQ_CONNECT, "weld": EQ_WELD, "joint": EQ_JOINT}
+_DEFAULT_POLYCOEF = (0.0, 1.0, 0.0, 0.0, 0.0)
+
+
+def _compile_equality(m, root, defaults):
+    """
+    ``<equality>``: the ACTIVE elements as ``eq_*`` arrays (MuJoCo 2.3.7 semantics and defaults: solref 0.02 1, solimp
+    0.9 0.95 0.001 0.5 2, polycoef 0 1 0 0 0; ``<default><equality>`` applies to every kind). Inactive elements are dropped. A joint
+    equality keeps ``eq_obj1id`` / ``eq_obj2id`` = joint ids (-1 = no ``joint2``) and its polycoef in ``eq_data``; a connect / weld
+    keeps its body ids (``eq_data`` unused): the lowering refuses those.
+    """
+    rows = []
+    eq = root.find("equality")
+    for el in ([] if eq is None else list(eq)):
+        if el.tag not in _EQ_TYPES:
+            raise NotImplementedError("equality element <%s> is not supported" % el.tag)
+        a = defaults.resolve("equality", el, None)
+        if a.get("active", "true") == "false":
+            continue
+        kind = _EQ_TYPES[el.tag]
+        if kind == EQ_JOINT:
+            o1, o2 = m.jnt_id(a["joint1"]), (m.jnt_id(a["joint2"]) if "joint2" in a else -1)
+            data = np.array(_DEFAULT_POLYCOEF)
+            if "polycoef" in a:
+                f = _floats(a["polycoef"])
+                data[:len(f)] = f
+        else:
+            o1 = m.body_id(a["body1"])
+            o2 = m.body_id(a["body2"]) if "body2" in a else 0
+            data = np.zeros(5)
+        rows.append(dict(name=a.get("name", "equality%d" % len(rows)), type=kind, obj1=o1, obj2=o2, data=data,
+                         solref=_floats(a.get("solref", "%g %g" % _DEFAULT_SOLREF), 2), solimp=_pad_solimp(a.get("solimp"))))
+    m.eq_names = [r["name"] for r in rows]
+    m.eq_type = np.array([r["type"] for r in rows], dtype=np.int32)
+    m.eq_obj1id = np.array([r["obj1"] for r in rows], dtype=np.int32)
+    m.eq_obj2id = np.array([r["obj2"] for r in rows], dtype=np.int32)
+    m.eq_data = np.array([r["data"] for r in rows]).reshape(-1, 5)
+    m.eq_solref = np.array([r["solref"] for r in rows]).reshape(-1, 2)
+    m.eq_solimp = np.array([r["solimp"] for r in rows]).reshape(-1, 5)
 
 
 def _orientation(attrs):
