@@ -28,6 +28,10 @@
  *                          utils/reward.py:66-117, evaluated on the previous observation)
  *   lm_set_reset_table  <- Trajectory.reset_trajectory + set_sim_state for finished episodes
  *                          (utils/trajectory.py:236-273, base.py:178-203), done on the device
+ *   lm_set_terminal_obs / lm_get_terminal_obs / lm_pinned_terminal_obs <- the observation an episode ENDED in: the reference's
+ *                          step() returns it itself, because its reset() is a call of its own (base.py:344-373); with device-side
+ *                          restarts the step's observation is already the new episode's, and the terminal one lands in a buffer
+ *                          [n_envs][nobs] of its own (device memory, the batch's or the caller's; off by default)
  *   lm_rollout          <- the user's `for step in range(n): env.step(a)` loop
  *                          (tests/test_environments.py:15-38), kept on the device for benchmarking
  *   lm_rollout_fused    <- the same loop with several control steps per kernel launch (policy-free only)
@@ -174,8 +178,9 @@ int lm_get_activation(lm_batch* b, float* act);
    obs [n_envs][nobs], reward [n_envs], done [n_envs] may each be NULL. Synchronous.
    The done byte: bit 0 (value 1) = absorbing state (the reference's `absorbing`: is_absorbing(obs), base.py:274-282);
    bit 1 (value 2) = the episode ended in this step on the device's side — it was restarted from the reset table (the
-   observation written is then the first of the NEW episode), or, without device-side restarts, this is the step that reached
-   the horizon. `done & 1` is what the reference's step() returns; `done != 0` mixes truncation into it. */
+   observation written is then the first of the NEW episode; the one it ended in is written to the terminal-observation
+   buffer, lm_set_terminal_obs), or, without device-side restarts, this is the step that reached the horizon (the terminal
+   buffer then receives a copy of that step's observation). `done & 1` is what the reference's step() returns; `done != 0` mixes truncation into it. */
 int lm_step(lm_batch* b, const float* action, float* obs, float* reward, uint8_t* done);
 
 /* the same step with DEVICE pointers (action [n_envs][nu], obs [n_envs][nobs], reward [n_envs], done [n_envs]; any may be
@@ -183,6 +188,27 @@ int lm_step(lm_batch* b, const float* action, float* obs, float* reward, uint8_t
    on (NULL: the library's own stream); with sync = 0 the call returns after the launch. The caller orders its own work
    against that stream. */
 int lm_step_device(lm_batch* b, const float* d_action, float* d_obs, float* d_reward, uint8_t* d_done, void* stream, int sync);
+
+/* TERMINAL OBSERVATIONS (off by default). Every control step whose done byte gets bit 1 writes the observation of the state the
+   step REACHED — the state the episode ended in — into row e of a device buffer [n_envs][nobs] float32, row-major like `obs`,
+   before the restart replaces state and goal: the goal columns hold the old episode's goal, the foot-force columns this step's mean
+   force (the fresh episode's observation reports zeros there). Rows of environments whose episode did not end are not written (an
+   inactive environment's neither): after lm_rollout / lm_rollout_fused a row holds the LAST episode end of its environment. A state
+   that ended because it became non-finite is stored as computed, NaN / Inf included (lm_stats.nan_resets counts those steps).
+     lm_set_terminal_obs    enabled = 1, d_out NULL: the batch allocates and owns the buffer, zero-filled by every such call;
+                            d_out non-NULL: a caller-owned DEVICE buffer (for users of lm_step_device; never freed by the library,
+                            and taken as given: at least [n_envs][nobs] float32 on the batch's device — size and device are NOT checked);
+                            enabled = 0: off again. Waits for every launch of this batch still in flight, those that lm_step_device
+                            queued on a caller's stream with sync = 0 included (the library's stream is ordered behind them).
+     lm_get_terminal_obs    the buffer -> host [n_envs][nobs] float32, stream-ordered behind the last step; an error when off
+     lm_pinned_terminal_obs with the feature on, every result set of lm_step_pinned's ring carries a fourth array, [n_envs][nobs]
+                            float64 in the column order of lm_set_obs_order: lm_step_pinned's conversion kernel fills the rows whose
+                            done byte has bit 1 (no extra copy is queued), the other rows keep what the slot held; an error when off.
+                            (Under an active list an inactive environment keeps the done byte of its last step: while that has bit 1
+                            its unchanged row is converted again, so the slot shows that environment's last episode end.) */
+int lm_set_terminal_obs(lm_batch* b, int enabled, float* d_out);
+int lm_get_terminal_obs(lm_batch* b, float* out);
+int lm_pinned_terminal_obs(lm_batch* b, int slot, double** term_obs);
 
 /* ACTIVE LIST: from now on every step / rollout of this batch runs only the listed environments (ids in [0, n_envs), each at most
    once; count 0: nothing runs), in one launch of ceil(count / environments per workgroup) workgroups; the others keep their state, and

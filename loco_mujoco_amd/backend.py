@@ -38,6 +38,7 @@ EXPORTS = ["lm_device_count", "lm_last_error", "lm_toolchain", "lm_model_create"
            "lm_batch_create", "lm_batch_destroy", "lm_batch_set_layout", "lm_batch_set_replay", "lm_batch_set_active", "lm_get_replay_marks", "lm_set_state", "lm_get_state", "lm_set_activation", "lm_get_activation",
            "lm_set_dof_params", "lm_get_dof_params", "lm_set_dof_randomization", "lm_set_goal", "lm_step", "lm_step_device",
            "lm_pinned_slot", "lm_set_obs_order", "lm_step_pinned",
+           "lm_set_terminal_obs", "lm_get_terminal_obs", "lm_pinned_terminal_obs",
            "lm_set_reset_table", "lm_set_auto_reset", "lm_rollout", "lm_rollout_fused", "lm_forward_debug", "lm_get_stats", "lm_sync",
            "lm_get_flags", "lm_set_model_variants", "lm_set_variant_index", "lm_get_variant_index", "lm_set_variant_rows",
            "lm_set_model_compiler", "lm_compile_models", "lm_get_model_draws", "lm_get_model_tables"]
@@ -85,6 +86,9 @@ def load_library():
     lib.lm_pinned_slot.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.POINTER(C.c_double)), C.POINTER(_U8)]
     lib.lm_set_obs_order.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int]
     lib.lm_step_pinned.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int]
+    lib.lm_set_terminal_obs.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    lib.lm_get_terminal_obs.argtypes = [C.c_void_p, _F]
+    lib.lm_pinned_terminal_obs.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.POINTER(C.c_double))]
     lib.lm_set_reset_table.argtypes = [C.c_void_p, _F, C.c_int, C.c_uint64, C.c_int64]
     lib.lm_set_auto_reset.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.lm_rollout.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.POINTER(Stats)]
@@ -172,6 +176,8 @@ class HipBatch:
         if getattr(self, "_h", None):
             self._lib.lm_batch_destroy(self._h)
             self._h = None
+        self._term_out = None              # a caller's terminal-observation tensor, the pinned ring's views
+        self._pinned = self._pinned_term = None
 
     __del__ = close
 
@@ -375,7 +381,9 @@ class HipBatch:
     def step_pinned(self, action64):
         """One control step through the library's float64 host surface (lm_step_pinned): ``action64`` is a C-contiguous float64
         array [n, nu]; returns (obs float64 [n, nobs], reward float64 [n], absorbing bool [n]). obs and reward are VIEWS of a ring of
-        PINNED_SLOTS pinned result sets owned by the batch: what a call returned stays intact for the next PINNED_SLOTS - 1 calls."""
+        PINNED_SLOTS pinned result sets owned by the batch: what a call returned stays intact for the next PINNED_SLOTS - 1 calls.
+        With terminal observations enabled a fourth view follows: float64 [n, nobs] in the order of set_obs_order, whose rows with
+        ``last_restarted`` set hold this step's terminal observation (the other rows: whatever the slot held)."""
         if getattr(self, "_pinned", None) is None:
             self._pinned = self._pinned_views()
             self._slot = -1
@@ -383,7 +391,55 @@ class HipBatch:
         _check(self._lib.lm_step_pinned(self._h, action64.ctypes.data_as(C.POINTER(C.c_double)), self._slot))
         obs, rew, done = self._pinned[self._slot]
         self.last_restarted = (done & 2) != 0
+        if getattr(self, "_term_on", False):
+            if getattr(self, "_pinned_term", None) is None:
+                self._pinned_term = self._pinned_term_views()
+            return obs, rew, (done & 1) != 0, self._pinned_term[self._slot]
         return obs, rew, (done & 1) != 0
+
+    def enable_terminal_obs(self, out=None):
+        """Terminal observations (``lm_set_terminal_obs``): a step that ends an episode on the device (done byte, bit 1) writes the
+        observation of the state it reached — not the restarted episode's first — into row e of a float32 buffer [n, nobs].
+        ``out`` None: a zero-filled buffer owned by the batch, read with :meth:`terminal_obs`; otherwise a device pointer (int) or a
+        torch tensor [n, nobs], float32, contiguous, which the batch keeps alive until :meth:`disable_terminal_obs` / :meth:`close`."""
+        ptr = None
+        if out is not None:
+            if hasattr(out, "data_ptr"):
+                if tuple(out.shape) != (self.n, self.nobs):
+                    raise ValueError("terminal observations: the buffer must be [%d, %d], not %s" % (self.n, self.nobs, tuple(out.shape)))
+                if "float32" not in str(out.dtype):
+                    raise ValueError("terminal observations: the buffer must be float32, not %s" % (out.dtype,))
+                if not out.is_contiguous():
+                    raise ValueError("terminal observations: the buffer must be contiguous")
+                if hasattr(out, "is_cuda") and not out.is_cuda:
+                    raise ValueError("terminal observations: the buffer must live on the device")
+                ptr = C.c_void_p(int(out.data_ptr()))
+            else:
+                ptr = C.c_void_p(int(out))
+        _check(self._lib.lm_set_terminal_obs(self._h, 1, ptr))
+        self._term_out = out
+        self._term_on = True
+
+    def disable_terminal_obs(self):
+        _check(self._lib.lm_set_terminal_obs(self._h, 0, None))
+        self._term_out = None
+        self._term_on = False
+
+    def terminal_obs(self):
+        """The terminal-observation buffer as a host float32 array [n, nobs] (the kernel's column order), after the last step."""
+        out = np.empty((self.n, self.nobs), dtype=np.float32)
+        _check(self._lib.lm_get_terminal_obs(self._h, _fp(out)))
+        return out
+
+    def _pinned_term_views(self):
+        views = []
+        for slot in range(self.PINNED_SLOTS):
+            t = C.POINTER(C.c_double)()
+            _check(self._lib.lm_pinned_terminal_obs(self._h, slot, C.byref(t)))
+            buf = (C.c_double * (self.n * self.nobs)).from_address(C.addressof(t.contents))
+            buf._owner = self
+            views.append(np.frombuffer(buf, dtype=np.float64).reshape(self.n, self.nobs))
+        return views
 
     def set_reset_table(self, rows, seed=0, global_env_offset=0):
         r = _f32(rows)

@@ -58,8 +58,8 @@ bool LM_CAT(launch_f, LM_FAMILY, p, LM_PART)(const LaunchCtx& L, const KArgs& a,
     if (!big) launch_one(step_kernel<3, 4, RK, true, -1>, grid, block, (size_t)lm::LaneMem<3, 4>::kGroup * groups, L, a);
     else launch_one(step_kernel<5, 8, RK, true, -1>, grid, block, (size_t)lm::LaneMem<5, 8>::kGroup * groups, L, a);
   } else if (kind == LMK_REP1) {
-    if (!big) launch_one(step_kernel<3, 4, RK, false, -1>, grid, block, (size_t)lm::LaneMem<3, 4>::kGroup * groups, L, a);
-    else launch_one(step_kernel<5, 8, RK, false, -1>, grid, block, (size_t)lm::LaneMem<5, 8>::kGroup * groups, L, a);
+    if (!big) launch_term(step_kernel<3, 4, RK, false, -1>, step_kernel<3, 4, RK, false, -1, 0, 0, 1, false, 0, true>, grid, block, (size_t)lm::LaneMem<3, 4>::kGroup * groups, L, a);
+    else launch_term(step_kernel<5, 8, RK, false, -1>, step_kernel<5, 8, RK, false, -1, 0, 0, 1, false, 0, true>, grid, block, (size_t)lm::LaneMem<5, 8>::kGroup * groups, L, a);
   } else return false;
   return true;
 #endif

@@ -76,6 +76,9 @@ struct lm_batch {
   float* h_act; unsigned char* h_out64[LM_PINNED_SLOTS]; int* d_perm; size_t out64_bytes;
   int* env_map; int n_active;    // active list (lm_batch_set_active): device copy of the environment ids, their number (N: all)
   float* mprc; int mprc_pairs;   // warm-start cache of the convex collider, [N][mprc_pairs][lm::kMprCacheFloats] (lm_step.h KArgs::mprc), or null
+  // terminal observations (lm_set_terminal_obs, lm_step.h KArgs::term_obs): the buffer the kernels write (null: off), the one the batch
+  // owns (null with a caller's buffer), and the fourth array of every pinned result set, [N][nobs] float64 (lm_pinned_terminal_obs)
+  float *term_obs, *term_own; double* h_term64[LM_PINNED_SLOTS];
 };
 // which kernel family serves a model (lm_family.hip): the quadruped family gets a specialised step kernel
 // <3 links, 6 slots, Euler, elliptic, self-collisions>; the humanoid families (five- and six-link chains) are compiled for
@@ -516,6 +519,8 @@ void lm_batch_destroy(lm_batch* b) {
                   b->vrec, b->vgt, b->vgpt, b->var, b->mc_ib, b->mc_db, b->vdirty, b->mc_mask, b->vgen, b->vdraws};
   for (void* p : bufs) if (p) (void)hipFree(p);
   if (b->d_perm) (void)hipFree(b->d_perm);
+  if (b->term_own) (void)hipFree(b->term_own);
+  for (int i = 0; i < LM_PINNED_SLOTS; i++) if (b->h_term64[i]) (void)hipHostFree(b->h_term64[i]);
   if (b->h_act) (void)hipHostFree(b->h_act);
   for (int i = 0; i < LM_PINNED_SLOTS; i++) if (b->h_out64[i]) (void)hipHostFree(b->h_out64[i]);
   if (b->ev0) (void)hipEventDestroy(b->ev0);
@@ -892,6 +897,7 @@ static KArgs make_args(lm_batch* b) {
   memset(&a, 0, sizeof(a));
   a.cm = b->m->d_cm; a.mt = b->m->d_mt; a.act = b->act; a.dofprm = b->dofprm; a.drspec = b->drspec;
   a.vrec = b->nvar > 0 ? b->vrec : nullptr; a.vgt = b->vgt; a.vgpt = b->vgpt; a.var = b->var; a.nvar = b->nvar; a.gpt_floats = b->gpt_floats; a.var_rows = b->var_rows; a.vdirty = b->mc_ib ? b->vdirty : nullptr; a.qpos = b->qpos; a.qvel = b->qvel; a.warm = b->warm; a.goal = b->goal;
+  a.term_obs = b->term_obs;
   a.ep_step = b->ep_step; a.ep_count = b->ep_count; a.flags = b->flags; a.slack = b->slack; a.mprc = b->mprc; a.mprc_pairs = b->mprc_pairs; a.env_map = b->env_map; a.n_active = b->n_active;
   a.table = b->table; a.table_rows = b->table_rows; a.seed = b->seed; a.env_offset = b->env_offset;
   a.auto_reset = b->auto_reset; a.horizon = b->horizon; a.step_index = b->step_index;
@@ -999,6 +1005,33 @@ __global__ void pack_out64_kernel(const float* __restrict__ obs, const float* __
   if (i < N) { r64[i] = (double)reward[i]; d8[i] = done[i]; }
 }
 
+// the same conversion with the terminal observations as the result set's fourth array: only the rows of the environments whose
+// episode ended in this step (done byte, bit 1) are converted — the others keep what the slot held. Under an active list the done
+// byte of an INACTIVE environment is the one of its last step: if that one had bit 1, its (unchanged) terminal row is converted
+// again every step — the slot then holds that environment's last episode end, as the device buffer does.
+__global__ void pack_out64_term_kernel(const float* __restrict__ obs, const float* __restrict__ reward, const unsigned char* __restrict__ done,
+                                       const float* __restrict__ term, const int* __restrict__ perm, int N, int nobs, double* __restrict__ o64,
+                                       double* __restrict__ r64, unsigned char* __restrict__ d8, double* __restrict__ t64) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x, total = N * nobs;
+  if (i < total) {
+    const int e = i / nobs, j = i - e * nobs, src = e * nobs + (perm ? perm[j] : j);
+    o64[i] = (double)obs[src];
+    if (done[e] & 2) t64[i] = (double)term[src];
+  }
+  if (i < N) { r64[i] = (double)reward[i]; d8[i] = done[i]; }
+}
+
+// the fourth array of the pinned result sets (allocated when both the ring and the terminal observations are in use)
+static int pinned_term_alloc(lm_batch* b) {
+  if (b->h_term64[0]) return 0;
+  const size_t bytes = sizeof(double) * (size_t)b->N * (size_t)b->m->T.nobs;
+  for (int i = 0; i < LM_PINNED_SLOTS; i++) {
+    HIPCHK(hipHostMalloc((void**)&b->h_term64[i], bytes, hipHostMallocDefault));
+    memset(b->h_term64[i], 0, bytes);
+  }
+  return 0;
+}
+
 static int pinned_alloc(lm_batch* b) {
   if (b->h_act) return 0;
   const size_t N = (size_t)b->N, nobs = (size_t)b->m->T.nobs;
@@ -1023,6 +1056,45 @@ int lm_pinned_slot(lm_batch* b, int slot, double** obs, double** reward, uint8_t
   return 0;
 }
 
+int lm_set_terminal_obs(lm_batch* b, int enabled, float* d_out) {
+  if (!b) return fail("null batch");
+  HIPCHK(hipSetDevice(b->m->device));
+  // no launch in flight still writes the buffer that is being replaced: the library's stream waits (ev_ext) for every launch that
+  // lm_step_device put on a caller's stream, so this wait covers those too
+  HIPCHK(hipStreamSynchronize(b->stream));
+  if (!enabled) { b->term_obs = nullptr; return 0; }
+  // the caller's device buffer (the batch's own, if any, is kept for later). Like the pointers of lm_step_device it is taken as given:
+  // [n_envs][nobs] float32 on this batch's device is the caller's promise, the library cannot check it
+  if (d_out) { b->term_obs = d_out; return 0; }
+  const size_t bytes = sizeof(float) * (size_t)b->N * (size_t)b->m->T.nobs;
+  if (!b->term_own) HIPCHK(hipMalloc(&b->term_own, bytes));
+  HIPCHK(hipMemsetAsync(b->term_own, 0, bytes, b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  b->term_obs = b->term_own;
+  return 0;
+}
+
+int lm_get_terminal_obs(lm_batch* b, float* out) {
+  if (!b) return fail("null batch");
+  if (!b->term_obs) return fail("terminal observations are not enabled (lm_set_terminal_obs)");
+  if (!out) return fail("lm_get_terminal_obs needs a host buffer [n_envs][nobs]");
+  HIPCHK(hipSetDevice(b->m->device));
+  // on the library's stream: behind every launch (one on a caller's stream included: ev_ext) and behind the replay kernel's pollers
+  HIPCHK(hipMemcpyAsync(out, b->term_obs, sizeof(float) * (size_t)b->N * (size_t)b->m->T.nobs, hipMemcpyDeviceToHost, b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
+int lm_pinned_terminal_obs(lm_batch* b, int slot, double** term_obs) {
+  if (!b) return fail("null batch");
+  HIPCHK(hipSetDevice(b->m->device));
+  if (slot < 0 || slot >= LM_PINNED_SLOTS) return fail("pinned slot out of range");
+  if (!b->term_obs) return fail("terminal observations are not enabled (lm_set_terminal_obs)");
+  if (pinned_alloc(b) || pinned_term_alloc(b)) return 1;
+  if (term_obs) *term_obs = b->h_term64[slot];
+  return 0;
+}
+
 int lm_set_obs_order(lm_batch* b, const int32_t* perm, int n) {
   HIPCHK(hipSetDevice(b->m->device));
   if (b->d_perm) { HIPCHK(hipStreamSynchronize(b->stream)); HIPCHK(hipFree(b->d_perm)); b->d_perm = nullptr; }
@@ -1040,6 +1112,7 @@ int lm_step_pinned(lm_batch* b, const double* action, int slot) {
   if (slot < 0 || slot >= LM_PINNED_SLOTS) return fail("pinned slot out of range");
   if (!action) return fail("lm_step_pinned needs an action (policy-free rollouts: lm_rollout)");
   if (pinned_alloc(b)) return 1;
+  if (b->term_obs && pinned_term_alloc(b)) return 1;
   const int N = b->N; const Task& T = b->m->T;
   const size_t na = (size_t)N * T.nu;
   for (size_t i = 0; i < na; i++) b->h_act[i] = (float)action[i];
@@ -1055,6 +1128,10 @@ int lm_step_pinned(lm_batch* b, const double* action, int slot) {
   b->step_index++;
   double* o64 = reinterpret_cast<double*>(b->h_out64[slot]);
   const int total = N * T.nobs, threads = 256;
+  if (b->term_obs)
+    hipLaunchKernelGGL(pack_out64_term_kernel, dim3((total + threads - 1) / threads), dim3(threads), 0, b->stream, b->obs, b->reward, b->done, b->term_obs,
+                       b->d_perm, N, T.nobs, o64, o64 + (size_t)N * T.nobs, reinterpret_cast<unsigned char*>(o64 + (size_t)N * T.nobs + N), b->h_term64[slot]);
+  else
   hipLaunchKernelGGL(pack_out64_kernel, dim3((total + threads - 1) / threads), dim3(threads), 0, b->stream, b->obs, b->reward, b->done,
                      b->d_perm, N, T.nobs, o64, o64 + (size_t)N * T.nobs, reinterpret_cast<unsigned char*>(o64 + (size_t)N * T.nobs + N));
   HIPCHK(hipGetLastError());

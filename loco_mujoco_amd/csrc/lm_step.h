@@ -191,6 +191,15 @@ struct KArgs {
   const int* env_map; int n_active;
   // debug (forward only)
   float* dM; float* dbias; float* dsmooth; float* dqacc_smooth; float* dqacc; float* dqfrc; int* dncon; int* diter;
+  // TERMINAL OBSERVATIONS (lm_set_terminal_obs): [N][nobs] like `obs`, or null (the default). A control step that ends an episode on
+  // the device's side — exactly the steps whose done byte gets bit 1 — writes the observation of the state it REACHED into its row here,
+  // before a restart replaces state and goal: the goal columns hold the old episode's goal, the foot-force columns this step's mean
+  // force (not the zeros of the fresh episode). Rows of environments whose episode goes on are not touched: after a rollout a row holds
+  // the LAST episode end of its environment. A state that ended because it became non-finite is stored as computed (NaN / Inf and all;
+  // DevStats::nan_resets counts those steps).
+  // Non-null selects the TERM instantiation of every kernel (launch_family): the default kernels do not contain the store and are,
+  // instruction for instruction, what they were without this field — which is why it is the LAST one (no other offset moves).
+  float* term_obs;
 };
 
 __device__ __forceinline__ unsigned long long mix64(unsigned long long x) {
@@ -254,7 +263,7 @@ __device__ __forceinline__ int replay_next(const KArgs& a, int& cursor) {
   }
 }
 
-template <int MC, int NS, bool RK4, bool FORWARD_ONLY, int CONE = -1, int NM = 0, int DR = 0, int REP = 1, bool FUSED = false, int PM = 0>
+template <int MC, int NS, bool RK4, bool FORWARD_ONLY, int CONE = -1, int NM = 0, int DR = 0, int REP = 1, bool FUSED = false, int PM = 0, bool TERM = false>
 __global__ __launch_bounds__(64) void step_kernel(KArgs a) {
   using QuadDpp = QuadDppT<REP>;
   constexpr bool PAIRS = PM != 0;
@@ -572,10 +581,39 @@ __global__ __launch_bounds__(64) void step_kernel(KArgs a) {
   float episodes = 0.0f;
   bool zero_act = false;                     // a restarted episode starts with zero muscle activation (mj_resetData)
   // done byte: bit 0 = absorbing state; bit 1 = the episode ended in this step on the device's side (restarted from the
-  // reset table — the observation written below is then the first of the NEW episode — or the horizon was reached)
+  // reset table — the observation written below is then the first of the NEW episode, the one it ended in goes to
+  // KArgs::term_obs — or the horizon was reached)
   // Without device-side restarts bit 1 is set in the ONE step that reaches the horizon, not in every later one.
   const bool restarts = a.auto_reset && a.table_rows > 0;
   const unsigned char done_byte = (unsigned char)((absorbing ? 1 : 0) | (((restarts && (trunc || absorbing)) || (!restarts && step_no == a.horizon)) ? 2 : 0));
+  if constexpr (TERM) {
+    // TERM instantiations only (KArgs::term_obs, chosen at launch): the observation this episode ENDED in — the columns of the regular
+    // store below from the state the step reached, the goal it ran under and this step's mean foot forces, before the restart branch
+    // replaces all three. A copy of that store and not a shared helper ON PURPOSE: everything outside this block is, token for token,
+    // the kernel without the feature, so the default instantiations keep their register allocation at the 512-register ceiling
+    // (DESIGN.md 4.1); tests/test_terminal_obs_gpu.py compares the two stores bitwise.
+    if ((done_byte & 2) && valid) {
+      float* o = a.term_obs + (long long)e * a.T.nobs;
+      if (c == 0) {
+#pragma unroll
+        for (int i = 0; i < 6; i++) { int iq = (int)RD(i, LM_D_QOBS), iv = (int)RD(i, LM_D_VOBS); if (iq >= 0) o[iq] = qr[i]; if (iv >= 0) o[iv] = vr[i]; }
+        for (int i = 0; i < a.T.ngoal; i++) o[a.T.nobs - a.T.ngrf - a.T.ngoal + i] = goal[i];
+      }
+#pragma unroll
+      for (int k = 0; k < MC; k++) if (k < nl) { int iq = (int)LK(k, LM_D_QOBS), iv = (int)LK(k, LM_D_VOBS); if (iq >= 0) o[iq] = qc[k]; if (iv >= 0) o[iv] = vc[k]; }
+      if (a.T.ngrf > 0) {
+        const float scale = 1.0f / (1000.0f * (float)a.T.nsub);      // this step's mean force, not the fresh episode's zeros
+        const int o0 = (int)cm[LM_CM_CHAINS + LM_C_GRF_OBS0 * LM_NCHAIN + c], o1 = (int)cm[LM_CM_CHAINS + LM_C_GRF_OBS1 * LM_NCHAIN + c];
+#pragma unroll
+        for (int j = 0; j < 3; j++) { if (o0 >= 0) o[o0 + j] = cnt.grf[0][j] * scale; if (o1 >= 0) o[o1 + j] = cnt.grf[1][j] * scale; }
+        if (MC >= 6) {
+          const int o2 = (int)cm[LM_CM_CHAINS + LM_C_GRF_OBS2 * LM_NCHAIN + c], o3 = (int)cm[LM_CM_CHAINS + LM_C_GRF_OBS3 * LM_NCHAIN + c];
+#pragma unroll
+          for (int j = 0; j < 3; j++) { if (o2 >= 0) o[o2 + j] = cnt.grf[2][j] * scale; if (o3 >= 0) o[o3 + j] = cnt.grf[3][j] * scale; }
+        }
+      }
+    }
+  }
   if (absorbing || trunc) {
     // without device-side restarts an episode that runs past its horizon (or stays absorbed) is counted once
     episodes = (a.auto_reset && a.table_rows > 0) || step_no == a.horizon || (absorbing && !trunc) ? 1.0f : 0.0f;
@@ -784,6 +822,13 @@ static void launch_one(K kernel, dim3 grid, dim3 block, size_t lane_floats, cons
   hipLaunchKernelGGL(kernel, grid, block, bytes, L.stream, a);
 }
 
+// the default kernel, or its TERM instantiation when the batch collects terminal observations (KArgs::term_obs)
+template <class K, class KT>
+static void launch_term(K kernel, KT kernel_term, dim3 grid, dim3 block, size_t lane_floats, const LaunchCtx& L, const KArgs& a) {
+  if (a.term_obs) launch_one(kernel_term, grid, block, lane_floats, L, a);
+  else launch_one(kernel, grid, block, lane_floats, L, a);
+}
+
 // one robot family = (links per chain MC, contact slots per chain NS, integrator, compiled-in cone, muscles per chain NM, pair
 // pass PM of the regular kernels: 0 none, 1 with the convex collider, 2 without — the replay kernel has it)
 template <int MC, int NS, bool RK4, int CONE, int NM, int PART, int PM = 0>
@@ -802,27 +847,27 @@ static bool launch_family(const LaunchCtx& L, const KArgs& a, int kind) {
     // L.epb carries the number of workgroups asked for here (pollers: a few; the drain pass: kReplayGrid). The statistics slots are
     // one per workgroup of the REGULAR launch (+ kReplayGrid for the pollers): not more workgroups than that
     const int ngroups = (int)((L.N + a.epb - 1) / a.epb), want = L.epb;
-    launch_one(step_kernel<MC, NSB, RK4, false, CONE, NM, PART, kReplayRep, true, PMB>, dim3(ngroups < want ? ngroups : want), dim3(4 * kReplayRep), (size_t)LMb::kPadded * 4, L, b);
+    launch_term(step_kernel<MC, NSB, RK4, false, CONE, NM, PART, kReplayRep, true, PMB>, step_kernel<MC, NSB, RK4, false, CONE, NM, PART, kReplayRep, true, PMB, true>, dim3(ngroups < want ? ngroups : want), dim3(4 * kReplayRep), (size_t)LMb::kPadded * 4, L, b);
     return true;
   }
   if constexpr (PART == 0) {
     // the forward-only (debug) kernel reads the cone at run time: full slot records (and always carries the convex collider)
     if (kind == LMK_FWD) launch_one(step_kernel<MC, NS, RK4, true, -1, NM, 0, 1, false, PMB>, grid, dim3(4 * L.epb),
                                     (size_t)lm::LaneMemFor<MC, NS, NM, (PM != 0), -1>::kGroup * ((4 * L.epb + 15) / 16), L, a);
-    else if (kind == LMK_REP4) launch_one(step_kernel<MC, NS, RK4, false, CONE, NM, 0, 4, false, PM>, grid, dim3(16 * L.epb), rep, L, a);
-    else if (kind == LMK_REP1) launch_one(step_kernel<MC, NS, RK4, false, CONE, NM, 0, 1, false, PM>, grid, dim3(4 * L.epb), plain, L, a);
+    else if (kind == LMK_REP4) launch_term(step_kernel<MC, NS, RK4, false, CONE, NM, 0, 4, false, PM>, step_kernel<MC, NS, RK4, false, CONE, NM, 0, 4, false, PM, true>, grid, dim3(16 * L.epb), rep, L, a);
+    else if (kind == LMK_REP1) launch_term(step_kernel<MC, NS, RK4, false, CONE, NM, 0, 1, false, PM>, step_kernel<MC, NS, RK4, false, CONE, NM, 0, 1, false, PM, true>, grid, dim3(4 * L.epb), plain, L, a);
     else return false;
   } else if constexpr (PART == 1) {
-    if (kind == LMK_DR_REP4) launch_one(step_kernel<MC, NS, RK4, false, CONE, NM, 1, 4, false, PM>, grid, dim3(16 * L.epb), rep, L, a);
-    else if (kind == LMK_DR_REP1) launch_one(step_kernel<MC, NS, RK4, false, CONE, NM, 1, 1, false, PM>, grid, dim3(4 * L.epb), plain, L, a);
-    else if (kind == LMK_FUSED) launch_one(step_kernel<MC, NS, RK4, false, CONE, NM, 0, 4, true, PM>, grid, dim3(16 * L.epb), rep, L, a);
-    else if (kind == LMK_FUSED_DR) launch_one(step_kernel<MC, NS, RK4, false, CONE, NM, 1, 4, true, PM>, grid, dim3(16 * L.epb), rep, L, a);
+    if (kind == LMK_DR_REP4) launch_term(step_kernel<MC, NS, RK4, false, CONE, NM, 1, 4, false, PM>, step_kernel<MC, NS, RK4, false, CONE, NM, 1, 4, false, PM, true>, grid, dim3(16 * L.epb), rep, L, a);
+    else if (kind == LMK_DR_REP1) launch_term(step_kernel<MC, NS, RK4, false, CONE, NM, 1, 1, false, PM>, step_kernel<MC, NS, RK4, false, CONE, NM, 1, 1, false, PM, true>, grid, dim3(4 * L.epb), plain, L, a);
+    else if (kind == LMK_FUSED) launch_term(step_kernel<MC, NS, RK4, false, CONE, NM, 0, 4, true, PM>, step_kernel<MC, NS, RK4, false, CONE, NM, 0, 4, true, PM, true>, grid, dim3(16 * L.epb), rep, L, a);
+    else if (kind == LMK_FUSED_DR) launch_term(step_kernel<MC, NS, RK4, false, CONE, NM, 1, 4, true, PM>, step_kernel<MC, NS, RK4, false, CONE, NM, 1, 4, true, PM, true>, grid, dim3(16 * L.epb), rep, L, a);
     else return false;
   } else {
     // per-environment joint parameters AND model variants (lm_set_model_variants)
-    if (kind == LMK_DRV_REP4) launch_one(step_kernel<MC, NS, RK4, false, CONE, NM, 2, 4, false, PM>, grid, dim3(16 * L.epb), rep, L, a);
-    else if (kind == LMK_DRV_REP1) launch_one(step_kernel<MC, NS, RK4, false, CONE, NM, 2, 1, false, PM>, grid, dim3(4 * L.epb), plain, L, a);
-    else if (kind == LMK_FUSED_DRV) launch_one(step_kernel<MC, NS, RK4, false, CONE, NM, 2, 4, true, PM>, grid, dim3(16 * L.epb), rep, L, a);
+    if (kind == LMK_DRV_REP4) launch_term(step_kernel<MC, NS, RK4, false, CONE, NM, 2, 4, false, PM>, step_kernel<MC, NS, RK4, false, CONE, NM, 2, 4, false, PM, true>, grid, dim3(16 * L.epb), rep, L, a);
+    else if (kind == LMK_DRV_REP1) launch_term(step_kernel<MC, NS, RK4, false, CONE, NM, 2, 1, false, PM>, step_kernel<MC, NS, RK4, false, CONE, NM, 2, 1, false, PM, true>, grid, dim3(4 * L.epb), plain, L, a);
+    else if (kind == LMK_FUSED_DRV) launch_term(step_kernel<MC, NS, RK4, false, CONE, NM, 2, 4, true, PM>, step_kernel<MC, NS, RK4, false, CONE, NM, 2, 4, true, PM, true>, grid, dim3(16 * L.epb), rep, L, a);
     else return false;
   }
   return true;

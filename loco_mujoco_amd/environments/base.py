@@ -128,6 +128,8 @@ class LocoEnv:
         self._backend = None           # created on first use (needs a GPU)
         self._pending_state = False
         self._auto_reset = False
+        self._terminal_obs = False       # enable_auto_reset(terminal_observations=True): step() reports info["terminal_observation"]
+        self._term32, self._term64 = {}, None
         self._n_models = 1
         self._current_model_idx = 0
         self._blocks = False             # several models in one BATCH: contiguous blocks of environments, one per model
@@ -590,6 +592,10 @@ class LocoEnv:
             if self._grouped:
                 obs32 = rew32 = done = None
                 restarted = np.zeros(self.n_envs, dtype=bool)
+                if self._terminal_obs:
+                    if getattr(self, "_grouped_term", None) is None:
+                        self._grouped_term = np.zeros((self.n_envs, self.backend.nobs), dtype=np.float32)
+                    term_rows = self._grouped_term
                 for idx in range(self._n_models):
                     envs = self._model_envs(idx)
                     if len(envs) == 0:
@@ -601,6 +607,11 @@ class LocoEnv:
                         obs32, rew32, done = np.zeros_like(o), np.zeros_like(r), np.zeros_like(d)
                     obs32[envs], rew32[envs], done[envs] = o[envs], r[envs], d[envs]
                     restarted[envs] = self.backend.last_restarted[envs]
+                    if self._terminal_obs and restarted[envs].any():
+                        # the observations these episodes ended in, from the batch of the model they ran on (before the host redraws
+                        # model and start row below)
+                        ended = envs[restarted[envs]]
+                        term_rows[ended] = self.backend.terminal_obs()[ended]
                 self._grouped_restarted = restarted
                 self._redrawn = None
                 if self._auto_reset and restarted.any():
@@ -611,7 +622,11 @@ class LocoEnv:
                 for idx in range(self._n_models):
                     self._select_model(idx)
                     parts.append(self.backend.step(a[self._model_envs(idx)]))
+                    if self._terminal_obs:
+                        parts[-1] = parts[-1] + (self._fetch_terminal(idx),)
                 obs32, rew32, done = (np.concatenate([p[i] for p in parts]) for i in range(3))
+                if self._terminal_obs:
+                    term32 = np.concatenate([p[3] for p in parts])
         else:
             b = self.backend
             if self._pending_state:
@@ -625,14 +640,20 @@ class LocoEnv:
                 if not getattr(b, "_obs_order_set", False):
                     b.set_obs_order(self._obs_perm())
                     b._obs_order_set = True
-                obs, reward, done = b.step_pinned(np.ascontiguousarray(a))
+                res = b.step_pinned(np.ascontiguousarray(a))
+                obs, reward, done = res[:3]
                 self._obs = obs
                 restarted = self._restarted_flags()
                 info = {}
                 if restarted is not None and (self._auto_reset or restarted.any()):
                     info = {"episode_restarted": restarted}
+                    if self._terminal_obs:
+                        # a view of the ring's fourth array: rows with episode_restarted set hold this step's terminal observation
+                        info["terminal_observation"] = res[3]
                 return obs, reward, done, info
             obs32, rew32, done = b.step(a)
+            if self._terminal_obs:
+                term32 = self._fetch_terminal(0)
         obs = obs32.astype(np.float64)
         perm = self._obs_perm()
         if perm is not None:
@@ -667,9 +688,25 @@ class LocoEnv:
         if restarted is not None and (self._auto_reset or restarted.any()):
             # always present with device-side restarts enabled (all False in most steps): a stable key for learners
             info = {"episode_restarted": restarted if self.n_envs > 1 else bool(restarted[0])}
+            if self._terminal_obs:
+                # the observation each finished episode ENDED in (the device's buffer holds every environment's last one), float64 in
+                # the reference's column order like `obs`; meaningful where episode_restarted is set
+                # (converted again only after a step that ended an episode: the rows change in no other step)
+                if self._term64 is None or np.any(restarted):
+                    term = (self._grouped_term if self._grouped else term32).astype(np.float64)
+                    self._term64 = term[:, perm] if perm is not None else term
+                term = self._term64.copy()                  # a fresh array, like `obs`: the caller may keep or edit it
+                info["terminal_observation"] = term if self.n_envs > 1 else (term[0] if restarted[0] else None)
         if self.n_envs == 1:
             return obs[0].copy(), float(reward[0]), bool(done[0]), info
         return obs.copy(), reward, done, info
+
+    def _fetch_terminal(self, idx):
+        """The selected batch's terminal-observation buffer on the host (float32, device column order). The device writes a row only
+        in a step that ends an episode, so the copy is made again only after such a step of this batch."""
+        if idx not in self._term32 or self.backend.last_restarted.any():
+            self._term32[idx] = self.backend.terminal_obs()
+        return self._term32[idx]
 
     def _restarted_flags(self):
         """bit 1 of the device's done byte per environment (episode restarted / horizon reached in the last step)."""
@@ -769,11 +806,17 @@ class LocoEnv:
         """(n_envs, n_goal) constants appended to the device observation, or None."""
         return None
 
-    def enable_auto_reset(self, seed=0, horizon=None, global_env_offset=0):
+    def enable_auto_reset(self, seed=0, horizon=None, global_env_offset=0, terminal_observations=False):
         """
         Device-side episode handling for batched rollouts: finished environments restart from a random
         trajectory sample inside the step kernel (counter-based RNG keyed by global env id, so results
         do not depend on how environments are sharded over GPUs).
+
+        ``terminal_observations=True``: ``step()`` adds ``info["terminal_observation"]``, [n_envs, nobs] float64 in the observation's
+        column order — where ``info["episode_restarted"]`` is set, the observation of the state the finished episode ENDED in (the
+        observation ``step()`` returns there is the first of the new episode); other rows hold earlier episode ends or zeros. On the
+        pinned path it is a view of the result ring like ``obs`` (a fresh array under ``copy_outputs=True``). ``n_envs=1``: a 1-D
+        array, or None when the episode did not end in this step.
         """
         if self.trajectories is None:
             raise ValueError("auto reset needs trajectory data")
@@ -805,6 +848,13 @@ class LocoEnv:
                 # seed started their first episodes on identical models)
                 b.compile_models()
             b.set_auto_reset(True, self.info.horizon if horizon is None else horizon)
+            if terminal_observations:
+                b.enable_terminal_obs()
+            elif getattr(b, "_term_on", False):
+                b.disable_terminal_obs()
+        self._terminal_obs = bool(terminal_observations)
+        self._grouped_term = None
+        self._term32, self._term64 = {}, None        # host copies of the terminal buffers (per batch) and their float64 form
         self._auto_reset = True
 
     def _reset_table(self):
