@@ -138,7 +138,8 @@ int lm_set_dof_params(lm_batch* b, const float* damping, const float* stiffness,
                       const uint8_t* mask);
 int lm_get_dof_params(lm_batch* b, float* damping, float* stiffness, float* frictionloss);
 /* redraw rule used when the device restarts an episode (lm_set_auto_reset): spec[3][nv][3] = (kind, a, b) per parameter
-   (damping, stiffness, frictionloss) and dof; kind 0 keep, 1 max(N(a,b),0), 2 U(a,b), 3 N(a,b). NULL disables. */
+   (damping, stiffness, frictionloss) and dof; kind 0 keep, 1 max(N(a,b),0), 2 U(a,b), 3 max(N(a,b),0) as well (both normal
+   kinds are clipped at 0: a joint parameter cannot be negative, utils/domain_randomization.py:335-337). NULL disables. */
 int lm_set_dof_randomization(lm_batch* b, const float* spec);
 /* model variants: what the reference's domain randomisation changes by re-compiling the model with other inertial / armature /
    geom-friction numbers (utils/domain_randomization.py:386-514 set_geom_conf / set_inertial_conf, base.py:183-185). The host
@@ -243,7 +244,10 @@ int lm_set_reset_table(lm_batch* b, const float* rows, int n_rows, uint64_t seed
 int lm_set_auto_reset(lm_batch* b, int enabled, int horizon);
 
 /* n_steps control steps entirely on the device. action_mode 0: zero action; 1: a ~ U(-1,1)^nu from
-   the counter-based RNG. Accumulates into *stats (may be NULL). */
+   the counter-based RNG, keyed by (seed, global env id, the batch's count of control steps so far, action index).
+   The call runs under the batch's seed (lm_set_reset_table; 0 without a table) xor `seed` * 0x9E3779B97F4A7C15:
+   that seed keys the actions AND the restart draws of these steps, so seed 0 restarts like lm_step does and
+   another seed draws other restart rows too. Accumulates into *stats (may be NULL). */
 int lm_rollout(lm_batch* b, int n_steps, int action_mode, uint64_t seed, lm_stats* stats);
 
 /* The same rollout with `steps_per_launch` control steps per kernel launch: every environment advances on its own, without
