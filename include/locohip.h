@@ -34,7 +34,10 @@
  *                          [n_envs][nobs] of its own (device memory, the batch's or the caller's; off by default)
  *   lm_rollout          <- the user's `for step in range(n): env.step(a)` loop
  *                          (tests/test_environments.py:15-38), kept on the device for benchmarking
- *   lm_rollout_fused    <- the same loop with several control steps per kernel launch (policy-free only)
+ *   lm_rollout_fused    <- the same loop with several control steps per kernel launch (zero or in-kernel random actions)
+ *   lm_rollout_tape     <- the same loop over a GIVEN action sequence, `for a in actions: env.step(a)` with no policy decision
+ *                          inside (action repeat / frame skip, K-step action chunks, sampling planners, open-loop replay of
+ *                          recorded actions), with every step's observation, reward and done byte recorded
  *   lm_forward_debug    <- mujoco.mj_forward (base.py:362) with intermediate results, for parity tests
  *
  * All arrays at the boundary are caller-owned HOST buffers, row-major [n_envs][dim], float32.
@@ -252,9 +255,36 @@ int lm_rollout(lm_batch* b, int n_steps, int action_mode, uint64_t seed, lm_stat
 
 /* The same rollout with `steps_per_launch` control steps per kernel launch: every environment advances on its own, without
    the device-wide join that ends each single-step launch with its slowest environment. Bitwise the same states,
-   observations and statistics as lm_rollout (which is steps_per_launch = 1); only for the policy-free action modes, a
-   policy in the loop needs lm_step / lm_step_device. */
+   observations and statistics as lm_rollout (which is steps_per_launch = 1). It keeps the LAST step's observation, reward and done
+   byte; actions that are known ahead for several steps go through lm_rollout_tape, a policy that decides every step needs
+   lm_step / lm_step_device. */
 int lm_rollout_fused(lm_batch* b, int n_steps, int steps_per_launch, int action_mode, uint64_t seed, lm_stats* stats);
+
+/* ACTION TAPES: n_steps control steps under given actions, `steps_per_launch` of them per kernel launch, every step recorded.
+     d_actions            DEVICE float32 [n_steps][n_envs][nu] with action_step_stride = n_envs * nu (floats from one step's actions to
+                          the next), or [n_envs][nu] with action_step_stride = 0: the same action in every step (action repeat).
+                          NULL and any other stride are errors.
+     d_obs, d_reward, d_done, d_term
+                          DEVICE tapes [n_steps][n_envs][nobs] float32, [n_steps][n_envs] float32, [n_steps][n_envs] bytes and
+                          [n_steps][n_envs][nobs] float32; each may be NULL. Step t writes row t. A NULL d_obs / d_reward / d_done
+                          means what it means in lm_step_device: the batch's own [n_envs] rows, which then hold the last step's.
+                          d_term receives the terminal observation of exactly the steps whose done byte has bit 1, at [t][e] (the
+                          other rows are not touched); it needs lm_set_terminal_obs enabled — otherwise the call fails and launches
+                          nothing. While d_term is given those rows go to the tape and NOT to the buffer of lm_set_terminal_obs;
+                          with d_term NULL that buffer is written as by lm_step_device.
+   The final state, every tape row and the statistics' event counters are bitwise what n_steps calls of lm_step_device fed
+   d_actions[t] produce, whatever steps_per_launch is, a ragged last launch included. Two statistics are not event counters and
+   follow the launches instead. lm_stats.reward_sum is a float32 sum per workgroup, and a fused launch adds up its own steps'
+   rewards first: it agrees to rounding, while every single reward in the tape is bitwise. replayed_env_steps counts where a step
+   ran: an environment handed to the replay kernel finishes its launch there, so the figure grows with steps_per_launch, as under
+   lm_rollout_fused. The call runs under the batch's own seed and advances its count of control steps by n_steps, so episodes
+   restart exactly as under lm_step.
+   Layouts of more than 4 environments per workgroup, families without replicas and batches with the model compiler run one step
+   per launch (as in lm_rollout_fused), with the same results. Under an active list the rows of inactive environments are left as
+   they were in every tape. `stream`, `sync`: as in lm_step_device. With sync != 0 and stats != NULL the statistics are drained
+   into *stats (kernel_ms: this call's, by HIP events); with sync = 0 *stats is not written. */
+int lm_rollout_tape(lm_batch* b, int n_steps, int steps_per_launch, const float* d_actions, long long action_step_stride,
+                    float* d_obs, float* d_reward, uint8_t* d_done, float* d_term, void* stream, int sync, lm_stats* stats);
 
 /* Validity flags of the LAST control step, one byte per environment: 1 = a contact was dropped (the chain's contact slots were
  * full), 2 = two geoms of the robot WITHOUT a pair collider (a box or cylinder against another geom) came within the contact

@@ -39,7 +39,7 @@ EXPORTS = ["lm_device_count", "lm_last_error", "lm_toolchain", "lm_model_create"
            "lm_set_dof_params", "lm_get_dof_params", "lm_set_dof_randomization", "lm_set_goal", "lm_step", "lm_step_device",
            "lm_pinned_slot", "lm_set_obs_order", "lm_step_pinned",
            "lm_set_terminal_obs", "lm_get_terminal_obs", "lm_pinned_terminal_obs",
-           "lm_set_reset_table", "lm_set_auto_reset", "lm_rollout", "lm_rollout_fused", "lm_forward_debug", "lm_get_stats", "lm_sync",
+           "lm_set_reset_table", "lm_set_auto_reset", "lm_rollout", "lm_rollout_fused", "lm_rollout_tape", "lm_forward_debug", "lm_get_stats", "lm_sync",
            "lm_get_flags", "lm_set_model_variants", "lm_set_variant_index", "lm_get_variant_index", "lm_set_variant_rows",
            "lm_set_model_compiler", "lm_compile_models", "lm_get_model_draws", "lm_get_model_tables"]
 
@@ -93,6 +93,8 @@ def load_library():
     lib.lm_set_auto_reset.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.lm_rollout.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.POINTER(Stats)]
     lib.lm_rollout_fused.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(Stats)]
+    lib.lm_rollout_tape.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_int, C.POINTER(Stats)]
     lib.lm_forward_debug.argtypes = [C.c_void_p, _F, C.POINTER(ForwardOut)]
     lib.lm_get_stats.argtypes = [C.c_void_p, C.POINTER(Stats), C.c_int]
     lib.lm_sync.argtypes = [C.c_void_p]
@@ -131,6 +133,67 @@ def _mask(mask, n):
         return None, None
     m = np.ascontiguousarray(mask, dtype=np.uint8).reshape(n)
     return m, m.ctypes.data_as(_U8)
+
+
+def check_tape_args(n, nu, nobs, actions, obs=None, reward=None, done=None, terminal=None, steps_per_launch=None, repeat=None,
+                    n_steps=None, terminal_enabled=True):
+    """The argument checks of :meth:`HipBatch.rollout_tape`, without a device: returns ``(T, action_step_stride, steps_per_launch)``
+    or raises ValueError. Buffers are objects with ``shape`` / ``dtype`` / ``is_contiguous()`` / ``data_ptr()`` (torch tensors), which
+    are checked, or raw device pointers (ints), which are taken as given and need ``n_steps`` (a tape) or ``repeat``."""
+    def described(x):
+        return hasattr(x, "data_ptr")
+
+    for name, x in (("actions", actions), ("obs", obs), ("reward", reward), ("done", done), ("terminal", terminal)):
+        if x is not None and not described(x) and (isinstance(x, bool) or not isinstance(x, (int, np.integer))):
+            raise ValueError("rollout_tape: %s must be a device tensor (data_ptr()) or a raw device pointer (int), not %s" % (name, type(x).__name__))
+
+    def check(name, x, shape, dtype):
+        if x is None or not described(x):
+            return
+        if tuple(x.shape) != tuple(shape):
+            raise ValueError("rollout_tape: %s must be %s, not %s" % (name, list(shape), list(x.shape)))
+        if dtype not in str(x.dtype):
+            raise ValueError("rollout_tape: %s must be %s, not %s" % (name, dtype, x.dtype))
+        if not x.is_contiguous():
+            raise ValueError("rollout_tape: %s must be contiguous" % name)
+        if hasattr(x, "is_cuda") and not x.is_cuda:
+            raise ValueError("rollout_tape: %s must live on the device" % name)
+
+    if actions is None:
+        raise ValueError("rollout_tape: actions is None (policy-free rollouts: rollout())")
+    if repeat is not None:
+        T, stride = int(repeat), 0
+        if n_steps is not None and int(n_steps) != T:
+            raise ValueError("rollout_tape: n_steps and repeat disagree")
+        if described(actions) and len(actions.shape) != 2:
+            raise ValueError("rollout_tape: with repeat, actions must be [%d, %d], not %s" % (n, nu, list(actions.shape)))
+        check("actions", actions, (n, nu), "float32")
+    else:
+        if described(actions):
+            if len(actions.shape) != 3:
+                raise ValueError("rollout_tape: actions must be [T, %d, %d] (or [%d, %d] with repeat=T), not %s" % (n, nu, n, nu, list(actions.shape)))
+            T = int(actions.shape[0])
+            if n_steps is not None and int(n_steps) != T:
+                raise ValueError("rollout_tape: n_steps = %d, but the action tape holds T = %d steps" % (int(n_steps), T))
+        elif n_steps is None:
+            raise ValueError("rollout_tape: a raw action pointer needs n_steps (a tape) or repeat")
+        else:
+            T = int(n_steps)
+        stride = n * nu
+        check("actions", actions, (T, n, nu), "float32")
+    if T < 1:
+        raise ValueError("rollout_tape: T must be >= 1, not %d" % T)
+    for name, x, tail, dtype in (("obs", obs, (n, nobs), "float32"), ("reward", reward, (n,), "float32"), ("done", done, (n,), "uint8"),
+                                 ("terminal", terminal, (n, nobs), "float32")):
+        if x is not None and described(x) and len(x.shape) >= 1 and int(x.shape[0]) != T:
+            raise ValueError("rollout_tape: the %s tape holds %d steps, the actions T = %d" % (name, int(x.shape[0]), T))
+        check(name, x, (T,) + tail, dtype)
+    if terminal is not None and not terminal_enabled:
+        raise ValueError("rollout_tape: a terminal tape needs terminal observations enabled (enable_terminal_obs)")
+    spl = T if steps_per_launch is None else int(steps_per_launch)
+    if spl < 1:
+        raise ValueError("rollout_tape: steps_per_launch must be >= 1, not %d" % spl)
+    return T, stride, spl
 
 
 class HipModel:
@@ -455,6 +518,26 @@ class HipBatch:
         st = Stats()
         _check(self._lib.lm_rollout_fused(self._h, int(n_steps), int(steps_per_launch), int(action_mode), int(seed), C.byref(st)))
         return st.as_dict()
+
+    def rollout_tape(self, actions, obs=None, reward=None, done=None, terminal=None, steps_per_launch=None, repeat=None, stream=None,
+                     sync=True, n_steps=None):
+        """T control steps under GIVEN actions, ``steps_per_launch`` (default: T) of them per kernel launch, every step recorded
+        (``lm_rollout_tape``). Buffers are torch tensors or raw device pointers, as in :meth:`step_device`: ``actions`` float32
+        [T, n, nu] — or [n, nu] with ``repeat=T``, the same action T times — and, each optional, ``obs`` float32 [T, n, nobs],
+        ``reward`` float32 [T, n], ``done`` uint8 [T, n] (the bit field of :meth:`step_device`) and ``terminal`` float32 [T, n, nobs]
+        (needs :meth:`enable_terminal_obs`; row [t, e] is written where ``done[t, e] & 2``, the others are left as they were).
+        Bitwise what T calls of ``step_device`` produce. Returns the statistics (``sync=True``) or None."""
+        T, stride, spl = check_tape_args(self.n, self.nu, self.nobs, actions, obs, reward, done, terminal, steps_per_launch, repeat, n_steps,
+                                         terminal_enabled=getattr(self, "_term_on", False))
+
+        def ptr(x):
+            if x is None:
+                return None
+            return C.c_void_p(int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x))
+        st = Stats()
+        _check(self._lib.lm_rollout_tape(self._h, T, spl, ptr(actions), stride, ptr(obs), ptr(reward), ptr(done), ptr(terminal),
+                                         None if stream is None else C.c_void_p(int(stream)), int(bool(sync)), C.byref(st) if sync else None))
+        return st.as_dict() if sync else None
 
     def forward_debug(self, action):
         a = _f32(action, (self.n, self.nu))

@@ -1209,6 +1209,58 @@ int lm_rollout_fused(lm_batch* b, int n_steps, int steps_per_launch, int action_
   return 0;
 }
 
+int lm_rollout_tape(lm_batch* b, int n_steps, int steps_per_launch, const float* d_actions, long long action_step_stride,
+                    float* d_obs, float* d_reward, uint8_t* d_done, float* d_term, void* stream, int sync, lm_stats* stats) {
+  if (!b) return fail("null batch");
+  HIPCHK(hipSetDevice(b->m->device));
+  const long long N = b->N; const Task& T = b->m->T;
+  // every argument is checked before the first launch: a refused call leaves the batch as it was
+  if (n_steps < 0) return fail("lm_rollout_tape: n_steps must be >= 0");
+  if (steps_per_launch < 1) return fail("lm_rollout_tape: steps_per_launch must be >= 1");
+  if (!d_actions) return fail("lm_rollout_tape: d_actions is null (policy-free rollouts: lm_rollout_fused)");
+  if (action_step_stride != 0 && action_step_stride != N * T.nu) return fail("lm_rollout_tape: action_step_stride must be n_envs * nu (a tape) or 0 (action repeat)");
+  if (d_term && !b->term_obs) return fail("lm_rollout_tape: d_term needs terminal observations enabled (lm_set_terminal_obs)");
+  static const bool no_replicas = LM_PROBE_ENV("LM_NO_REPLICAS") != nullptr;
+  // as in lm_rollout_fused: one control step per launch where there is no fused kernel (the launch's pointers then carry the offsets)
+  if (b->epb > 4 || no_replicas || !family_has_replicas(b)) steps_per_launch = 1;
+  if (b->mc_ib) steps_per_launch = 1;
+  KArgs a = make_args(b);            // the batch's own seed: a tape launch restarts episodes exactly like lm_step*
+  a.action_mode = 0;
+  a.tape_action = action_step_stride;
+  // a tape that is not given: the batch's own rows as in lm_step_device, stride 0 — every control step overwrites them
+  a.tape_obs = d_obs ? N * T.nobs : 0; a.tape_reward = d_reward ? N : 0; a.tape_done = d_done ? N : 0; a.tape_term = d_term ? N * T.nobs : 0;
+  hipStream_t own = b->stream;
+  hipStream_t used = stream ? (hipStream_t)stream : own;
+  if (used != own) { HIPCHK(hipEventRecord(b->ev_ext, own)); HIPCHK(hipStreamWaitEvent(used, b->ev_ext, 0)); }
+  HIPCHK(hipEventRecord(b->ev0, used));
+  b->stream = used;
+  for (int s = 0; s < n_steps; s += steps_per_launch) {
+    a.nfused = (n_steps - s < steps_per_launch) ? n_steps - s : steps_per_launch;
+    a.step_index = b->step_index; b->step_index += (unsigned)a.nfused;
+    a.action = d_actions + (long long)s * action_step_stride;
+    a.obs = d_obs ? d_obs + (long long)s * N * T.nobs : b->obs;
+    a.reward = d_reward ? d_reward + (long long)s * N : b->reward;
+    a.done = d_done ? d_done + (long long)s * N : b->done;
+    if (d_term) a.term_obs = d_term + (long long)s * N * T.nobs;
+    launch_step(b, a);
+    if (g_launch_err) { b->stream = own; return fail(g_launch_err); }
+  }
+  b->stream = own;
+  HIPCHK(hipEventRecord(b->ev1, used));
+  HIPCHK(hipGetLastError());
+  if (used != own) { HIPCHK(hipEventRecord(b->ev_ext, used)); HIPCHK(hipStreamWaitEvent(own, b->ev_ext, 0)); }
+  if (!sync) return 0;
+  HIPCHK(hipEventSynchronize(b->ev1));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, b->ev0, b->ev1));
+  b->acc.kernel_ms += ms;
+  if (stats) {
+    if (drain_stats(b)) return 1;
+    *stats = b->acc; stats->kernel_ms = ms;
+  }
+  return 0;
+}
+
 int lm_rollout(lm_batch* b, int n_steps, int action_mode, uint64_t seed, lm_stats* stats) {
   return lm_rollout_fused(b, n_steps, 1, action_mode, seed, stats);
 }

@@ -200,6 +200,12 @@ struct KArgs {
   // Non-null selects the TERM instantiation of every kernel (launch_family): the default kernels do not contain the store and are,
   // instruction for instruction, what they were without this field — which is why it is the LAST one (no other offset moves).
   float* term_obs;
+  // TAPES (lm_rollout_tape; read by the FUSED instantiations only, the replay kernels among them): control step `fused` of a launch
+  // reads its action at action + fused * tape_action and stores at obs + fused * tape_obs, reward + fused * tape_reward, done +
+  // fused * tape_done and term_obs + fused * tape_term — floats (bytes for `done`) from one step's rows to the next: N*nu | N*nobs |
+  // N | N | N*nobs. 0 (the default, and the stride of a null pointer) = every step uses the same rows: the policy-free rollouts,
+  // action repeat, outputs that are not recorded.
+  long long tape_action, tape_obs, tape_reward, tape_done, tape_term;
 };
 
 __device__ __forceinline__ unsigned long long mix64(unsigned long long x) {
@@ -351,6 +357,11 @@ __global__ __launch_bounds__(64) void step_kernel(KArgs a) {
   for (int fused = 0; fused < (FUSED ? a.nfused : 1); fused++) {
   if (FUSED && fused > 0) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
   const unsigned step_index = a.step_index + (unsigned)fused;
+  // this control step's rows of the tapes (KArgs::tape_action; the single-step kernels: the launch's own pointers)
+  const float* const action_k = FUSED ? a.action + fused * a.tape_action : a.action;
+  float* const obs_k = FUSED ? a.obs + fused * a.tape_obs : a.obs;
+  float* const reward_k = FUSED ? a.reward + fused * a.tape_reward : a.reward;
+  unsigned char* const done_k = FUSED ? a.done + fused * a.tape_done : a.done;
   bool valid = valid0 && !gone && (!REPLAY || fused >= first_step);
   // ---- load state (root replicated in the 4 lanes: same address -> one transaction)
   float qr[6], vr[6], war[6], qc[MC], vc[MC], wac[MC], goal[4];
@@ -417,7 +428,7 @@ __global__ __launch_bounds__(64) void step_kernel(KArgs a) {
     int k = (int)kf;
     if (k < 0) return 0.0f;
     float act = 0.0f;
-    if (a.action_mode == 0 && a.action) act = a.action[(long long)e * a.T.nu + k];
+    if (a.action_mode == 0 && action_k) act = action_k[(long long)e * a.T.nu + k];
     else if (a.action_mode == 2) {
       unsigned long long r = mix64(a.seed ^ mix64((unsigned long long)gid * 0x100000001B3ull + step_index) ^ (unsigned long long)(k + 1) * 0xD6E8FEB86659FD93ull);
       act = (float)(r >> 40) * (2.0f / 16777216.0f) - 1.0f;
@@ -450,7 +461,7 @@ __global__ __launch_bounds__(64) void step_kernel(KArgs a) {
       const int k = (int)rec[LM_MU_ACT];
       float u = 0.0f;
       if (k >= 0) {
-        if (a.action_mode == 0 && a.action) u = a.action[(long long)e * a.T.nu + k];
+        if (a.action_mode == 0 && action_k) u = action_k[(long long)e * a.T.nu + k];
         else if (a.action_mode == 2) {
           unsigned long long r = mix64(a.seed ^ mix64((unsigned long long)gid * 0x100000001B3ull + step_index) ^ (unsigned long long)(k + 1) * 0xD6E8FEB86659FD93ull);
           u = (float)(r >> 40) * (2.0f / 16777216.0f) - 1.0f;
@@ -593,7 +604,7 @@ __global__ __launch_bounds__(64) void step_kernel(KArgs a) {
     // the kernel without the feature, so the default instantiations keep their register allocation at the 512-register ceiling
     // (DESIGN.md 4.1); tests/test_terminal_obs_gpu.py compares the two stores bitwise.
     if ((done_byte & 2) && valid) {
-      float* o = a.term_obs + (long long)e * a.T.nobs;
+      float* o = (FUSED ? a.term_obs + fused * a.tape_term : a.term_obs) + (long long)e * a.T.nobs;
       if (c == 0) {
 #pragma unroll
         for (int i = 0; i < 6; i++) { int iq = (int)RD(i, LM_D_QOBS), iv = (int)RD(i, LM_D_VOBS); if (iq >= 0) o[iq] = qr[i]; if (iv >= 0) o[iv] = vr[i]; }
@@ -678,8 +689,8 @@ __global__ __launch_bounds__(64) void step_kernel(KArgs a) {
 #pragma unroll
     for (int i = 0; i < 6; i++) { a.qpos[dr[i] * N + e] = qr[i]; a.qvel[dr[i] * N + e] = vr[i]; a.warm[dr[i] * N + e] = war[i]; }
     a.ep_step[e] = step_no;
-    if (a.reward) a.reward[e] = reward;
-    if (a.done) a.done[e] = done_byte;
+    if (reward_k) reward_k[e] = reward;
+    if (done_k) done_k[e] = done_byte;
   }
 #pragma unroll
   for (int k = 0; k < MC; k++) if (k < nl) { a.qpos[dc[k] * N + e] = qc[k]; a.qvel[dc[k] * N + e] = vc[k]; a.warm[dc[k] * N + e] = wac[k]; }
@@ -695,8 +706,8 @@ __global__ __launch_bounds__(64) void step_kernel(KArgs a) {
       a.act[(long long)(int)mt[LM_MT_HEAD + (m0 + i) * LM_MU_SIZE + LM_MU_STATE] * N + e] = zero_act ? 0.0f : ((fabsf(v) < 1e30f) ? v : 0.0f);
     }
   }
-  if (a.obs) {
-    float* o = a.obs + (long long)e * a.T.nobs;
+  if (obs_k) {
+    float* o = obs_k + (long long)e * a.T.nobs;
     if (c == 0) {
 #pragma unroll
       for (int i = 0; i < 6; i++) { int iq = (int)RD(i, LM_D_QOBS), iv = (int)RD(i, LM_D_VOBS); if (iq >= 0) o[iq] = qr[i]; if (iv >= 0) o[iv] = vr[i]; }

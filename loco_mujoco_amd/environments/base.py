@@ -701,6 +701,79 @@ class LocoEnv:
             return obs[0].copy(), float(reward[0]), bool(done[0]), info
         return obs.copy(), reward, done, info
 
+    def _step_chunk_refusal(self):
+        """Why :meth:`step_chunk` cannot serve this environment (a reason), or None."""
+        if self._blocks or self._grouped:
+            return "several models in one batch (block / grouped batches) step one batch per model: call step() K times"
+        if self._use_model_compiler:
+            return ("the model compiler draws a fresh model at every device-side restart, between two launches: a chunk would run the "
+                    "new episode's first steps on the old model — call step() K times")
+        if self._reward_device_spec() is None:
+            return "the reward runs on the host after every step (custom functor / foot-force columns): call step() K times"
+        return None
+
+    def step_chunk(self, actions):
+        """
+        K control steps under K GIVEN actions — a loop over ``step()`` with no policy decision inside (action repeat, K-step action
+        chunks, sampling planners, open-loop replay) — in one library call, the K steps fused into one kernel launch
+        (``lm_rollout_tape``). ``actions``: float64 [K, n_envs, nu] ([K, nu] for one environment). Returns what K calls of ``step()``
+        return, stacked: ``obs`` [K, n_envs, nobs] float64 in the reference's column order, ``reward`` [K, n_envs], ``absorbing``
+        [K, n_envs] and ``info`` with ``episode_restarted`` [K, n_envs] under the conditions ``step()`` reports it and, with
+        ``enable_auto_reset(terminal_observations=True)``, ``terminal_observation`` [K, n_envs, nobs]: where ``episode_restarted`` is
+        set, the observation that episode ended in; the other rows are unspecified (zeros here; ``step()`` leaves whatever its buffer
+        held), as in ``step()``. All are fresh arrays (the leading axes stay for one environment too). ``step()`` and ``step_chunk()`` can alternate.
+        """
+        if self._obs is None:
+            raise RuntimeError("call reset() before step_chunk()")
+        why = self._step_chunk_refusal()
+        if why is not None:
+            raise NotImplementedError("step_chunk: " + why)
+        a = np.asarray(actions, dtype=np.float64)
+        if a.ndim == 2 and self.n_envs == 1:
+            a = a[:, None, :]
+        if a.ndim != 3 or a.shape[0] < 1 or a.shape[1] != self.n_envs:
+            raise ValueError("step_chunk: actions must be [K, %d, nu], not %s" % (self.n_envs, list(np.shape(actions))))
+        b = self.backend
+        if self._pending_state:
+            self._upload_state()
+        obs32, rew32, done, term32 = self._tape_through_host(a)
+        perm = self._obs_perm()
+        obs = obs32.astype(np.float64)
+        if perm is not None:
+            obs = obs[:, :, perm]
+        reward = rew32.astype(np.float64)
+        restarted = (done & 2) != 0
+        info = {}
+        if self._auto_reset or restarted.any():
+            info = {"episode_restarted": restarted}
+            if self._terminal_obs:
+                term = term32.astype(np.float64)
+                info["terminal_observation"] = term[:, :, perm] if perm is not None else term
+                # step()'s host copies of the terminal buffer are stale now: it fetches them again
+                self._term32, self._term64 = {}, None
+        self._obs = obs[-1].copy()
+        return obs, reward, (done & 1) != 0, info
+
+    def _tape_through_host(self, a):
+        """``HipBatch.rollout_tape`` for the host array ``a`` [K, n_envs, nu]: one copy up (float32), the tapes back as numpy arrays
+        (obs, reward, done byte, terminal or None). Rows of the terminal tape whose step ended no episode stay zero."""
+        import torch
+        b = self.backend
+        a32 = np.ascontiguousarray(a, dtype=np.float32)
+        if a32.shape[2] != b.nu:
+            raise ValueError("step_chunk: actions must be [K, %d, %d], not %s" % (b.n, b.nu, list(a32.shape)))
+        K, dev = a32.shape[0], torch.device("cuda", self._device)
+        d_a = torch.from_numpy(a32).to(dev)
+        d_obs = torch.empty((K, b.n, b.nobs), dtype=torch.float32, device=dev)
+        d_rew = torch.empty((K, b.n), dtype=torch.float32, device=dev)
+        d_done = torch.empty((K, b.n), dtype=torch.uint8, device=dev)
+        d_term = torch.zeros((K, b.n, b.nobs), dtype=torch.float32, device=dev) if self._terminal_obs else None
+        torch.cuda.synchronize(dev)            # the library's stream is not torch's: the buffers are ready before the launches
+        b.rollout_tape(d_a, obs=d_obs, reward=d_rew, done=d_done, terminal=d_term)
+        done = d_done.cpu().numpy()
+        b.last_restarted = (done[-1] & 2) != 0          # what step() reports as episode_restarted, kept current for _restarted_flags
+        return d_obs.cpu().numpy(), d_rew.cpu().numpy(), done, (d_term.cpu().numpy() if d_term is not None else None)
+
     def _fetch_terminal(self, idx):
         """The selected batch's terminal-observation buffer on the host (float32, device column order). The device writes a row only
         in a step that ends an episode, so the copy is made again only after such a step of this batch."""
