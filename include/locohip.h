@@ -111,7 +111,8 @@ int lm_model_dims(const lm_model* m, lm_dims* out);
 int lm_batch_create(lm_model* m, int n_envs, lm_batch** out);
 void lm_batch_destroy(lm_batch* b);
 /* Launch geometry (no counterpart in the reference: its step is one MjData at a time, base.py:185). envs_per_workgroup = 4: one wave
-   per 4 environments, each replicated over 4 quads (default); 8 or 16: plain layout without replicas. Same physics either way. */
+   per 4 environments, each replicated over 4 quads (default); 8 or 16: plain layout without replicas. Same physics either way.
+   Refused, with the byte counts, where a kernel of the layout needs more LDS than a compute unit has (lm_lds_bytes). */
 int lm_batch_set_layout(lm_batch* b, int envs_per_workgroup);
 /* Speculate / replay (no counterpart in the reference: the engine it calls sizes its contact buffers for everything,
    environments/data/humanoid/humanoid_torque.xml:19 njmax 1000 / nconmax 400, data/atlas/atlas.xml:23). The regular step kernels hold a few
@@ -299,6 +300,15 @@ int lm_forward_debug(lm_batch* b, const float* action, lm_forward_out* out);
    csrc/Makefile: no counterpart in the reference; the kernels sit at the 512-register ceiling, where one code-generation defect of the
    toolchain was met (csrc/Makefile) — a library built by another compiler should be re-validated (tests/test_abi_exports.py) */
 const char* lm_toolchain(void);
+/* LDS per workgroup, in bytes, of one step kernel: what it declares itself (static: the muscle table of the muscle families, the statistics
+   block) and what its launch asks for (dynamic: the model's constant table of cm_used_floats floats + lane memory). Host arithmetic from the
+   constants the launches use; no device is touched, nothing is launched. family: 0 quadruped, 2 / 4 five-link humanoids RK4 / Euler, 5
+   muscles, 6 generic, 7 six-link chains, 8 / 9 / 10 five-link chains with self-collisions RK4 / Euler / muscles, 11 seven-link chains.
+   kind: 0 forward (lm_forward_debug), 1 / 2 replicated / plain, 3 / 4 the same with joint parameters, 5 / 6 fused, 7 / 8 replicated /
+   plain with model variants, 9 fused with model variants, 10 / 11 / 12 the replay kernels. Non-zero: the family has no such kernel.
+   lm_batch_set_layout refuses a layout whose step kernels exceed a compute unit's LDS (160 KB on gfx950), lm_forward_debug its own kernel
+   (no counterpart in the reference: it has no launch geometry). */
+int lm_lds_bytes(int family, int kind, int envs_per_workgroup, int cm_used_floats, int* static_bytes, int* dynamic_bytes);
 
 int lm_get_stats(lm_batch* b, lm_stats* out, int reset);
 int lm_sync(lm_batch* b);

@@ -7,7 +7,9 @@ namespace lmk {
 #define LM_CAT2(a, b, c, d) a##b##c##d
 #define LM_CAT(a, b, c, d) LM_CAT2(a, b, c, d)
 
-bool LM_CAT(launch_f, LM_FAMILY, p, LM_PART)(const LaunchCtx& L, const KArgs& a, int kind) {
+bool LM_CAT(launch_f, LM_FAMILY, p, LM_PART)(const LaunchCtx& L0, const KArgs& a, int kind) {
+  LaunchCtx L = L0;
+  L.stat_bytes = static_lds_bytes(0);      // (the generic family below: no muscles; launch_family sets its own)
 #if LM_FAMILY == 0      // quadruped: thigh (2) + calf (2) + foot (1) floor contacts per leg + one for a self-contact, elliptic cones
 #ifndef LM_A1_NS
 #define LM_A1_NS 6

@@ -10,6 +10,7 @@ using lmk::KArgs; using lmk::Task; using lmk::DevStats; using lmk::LaunchCtx;
 namespace {
 thread_local std::string g_err;
 thread_local const char* g_launch_err = nullptr;
+thread_local std::string g_layout_err;
 int fail(const std::string& m) { g_err = m; return 1; }
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
 
@@ -34,6 +35,8 @@ struct lm_model {
   int nroot;
   std::vector<int> root_dofs;
   bool root_limited;         // a root dof with an active-able limit (lm_batch_set_replay)
+  size_t lds_limit;          // LDS of one CU in bytes: what the runtime reports, or kLdsAssumed where it reports the 64 KB default only
+  bool lds_reported;         // true: lds_limit is the runtime's figure
   bool root_xyz;             // the root's first three dofs are slides along +x, +y, +z in a root frame that is the world's (lm_core.h ROOT_XYZ)
 };
 
@@ -50,6 +53,7 @@ struct lm_batch {
   DevStats* stats;
   int table_rows; unsigned long long seed; long long env_offset; int auto_reset, horizon; unsigned step_index;
   int epb, nblocks;
+  int lds_ok[2];             // environments per workgroup at which the LDS of the step kernels [0] / the forward kernel [1] was found to fit (0: not checked yet)
   unsigned long long* timers;
   unsigned long long* tline;     // LM_TIMERS builds: time line of the last launch (lm_step.h KArgs::tline)
   hipStream_t stream;
@@ -116,6 +120,58 @@ static bool family_has_replicas(const lm_batch* b) { return family_of(b) != 6; }
 static bool family_has_pairs(int fam) { return fam == 0 || fam == 7 || fam == 8 || fam == 9 || fam == 10 || fam == 11; }
 static bool family_has_equality_rows(int fam) { return fam == 11; }
 
+constexpr size_t kLdsAssumed = 160 * 1024;      // LDS of a gfx950 CU (lm_core.h: LaneMem)
+
+static const lmk::family_fn kFamilyTable[lmk::LMK_NFAMILY][3] = {
+      {lmk::launch_f0p0, lmk::launch_f0p1, lmk::launch_f0p2}, {nullptr, nullptr, nullptr},
+      {lmk::launch_f2p0, lmk::launch_f2p1, lmk::launch_f2p2}, {nullptr, nullptr, nullptr},
+      {lmk::launch_f4p0, lmk::launch_f4p1, lmk::launch_f4p2}, {lmk::launch_f5p0, lmk::launch_f5p1, lmk::launch_f5p2},
+      {lmk::launch_f6p0, lmk::launch_f6p1, lmk::launch_f6p2}, {lmk::launch_f7p0, lmk::launch_f7p1, lmk::launch_f7p2},
+      {lmk::launch_f8p0, lmk::launch_f8p1, lmk::launch_f8p2}, {lmk::launch_f9p0, lmk::launch_f9p1, lmk::launch_f9p2},
+      {lmk::launch_f10p0, lmk::launch_f10p1, lmk::launch_f10p2}, {lmk::launch_f11p0, lmk::launch_f11p1, lmk::launch_f11p2}};
+
+// The LDS a launch of `kind` (lm_step.h LMK_*) of family `fam` takes at `epb` environments per workgroup for a model whose constant table
+// uses `cm_used` floats: asked of the launch code itself (LaunchCtx::probe — nothing is launched, no device is touched). false: the
+// family has no kernel of that kind.
+static bool lds_of(int fam, int kind, int epb, int cm_used, int max_links, lmk::LdsUse* out) {
+  if (fam < 0 || fam >= lmk::LMK_NFAMILY || !kFamilyTable[fam][0] || epb < 1) return false;
+  KArgs a;
+  memset(&a, 0, sizeof(a));
+  a.T.cm_used = cm_used; a.T.max_links = max_links; a.epb = epb; a.N = epb;
+  lmk::LdsUse u = {0, 0};
+  const LaunchCtx L = {nullptr, epb, epb, 0, nullptr, &u, 0};
+  for (int p = 0; p < 3; p++)
+    if (kFamilyTable[fam][p](L, a, kind) && u.stat + u.dyn > 0) { *out = u; return true; }
+  return false;
+}
+
+// Why the batch cannot step at `epb` environments per workgroup: the first kernel of that layout — regular, per-environment parameters,
+// model variants, fused, replay — whose static + dynamic LDS a CU cannot hold, with the byte counts; empty: all fit. `fwd`: the same
+// question for lm_forward_debug's kernel alone (run-time cone, full slot records: at 16 per workgroup it does not fit for most humanoid
+// models whose step kernels do, so lm_forward_debug is refused at its own call and not with the layout).
+static std::string layout_refusal(const lm_batch* b, int epb, bool fwd) {
+  const int fam = family_of(b);
+  if (fam < 0) return "";
+  const bool plain = epb > 4;
+  static const char* names[lmk::LMK_NKINDS] = {"forward", "replicated", "plain", "replicated, joint parameters", "plain, joint parameters", "fused", "fused, joint parameters",
+                                               "replicated, model variants", "plain, model variants", "fused, model variants", "replay", "replay, joint parameters", "replay, model variants"};
+  for (int kind = 0; kind < lmk::LMK_NKINDS; kind++) {
+    const bool rep4 = kind == lmk::LMK_REP4 || kind == lmk::LMK_DR_REP4 || kind == lmk::LMK_DRV_REP4 || kind == lmk::LMK_FUSED || kind == lmk::LMK_FUSED_DR || kind == lmk::LMK_FUSED_DRV;
+    const bool rep1 = kind == lmk::LMK_REP1 || kind == lmk::LMK_DR_REP1 || kind == lmk::LMK_DRV_REP1;
+    if ((kind == lmk::LMK_FWD) != fwd || (plain && rep4) || (!plain && rep1 && fam != 6)) continue;
+    lmk::LdsUse u;
+    if (!lds_of(fam, kind, epb, b->m->T.cm_used, b->m->T.max_links, &u)) continue;
+    if (u.stat + u.dyn > b->m->lds_limit) {
+      char why[400];
+      snprintf(why, sizeof(why), "%d environments per workgroup: the %s kernel of family %d needs %zu B of LDS per workgroup (%zu B static + %zu B dynamic, "
+               "%d B of it this model's constant table), a compute unit has %zu B (%s)", epb, names[kind], fam, u.stat + u.dyn, u.stat, u.dyn,
+               (int)sizeof(float) * b->m->T.cm_used, b->m->lds_limit, b->m->lds_reported ? "reported by the runtime" : "assumed: the runtime reports the 64 KB default only");
+      return why;
+    }
+  }
+  return "";
+}
+
 // (Round 5, tried and dropped: a one-workgroup GATE kernel in front of the regular launch that waits until the launch's pollers are
 // resident, and a higher priority for their stream. Launched first on their own stream the pollers lose the race for the chip in 7
 // launches of 10 and start when the first regular workgroups retire, 4.4 ms into a HumanoidTorque launch; with the gate they are
@@ -125,17 +181,16 @@ static bool family_has_equality_rows(int fam) { return fam == 11; }
 template <bool FWD>
 static void launch_variant(lm_batch* b, const KArgs& a) {
   static const bool no_replicas = LM_PROBE_ENV("LM_NO_REPLICAS") != nullptr;                  // A/B switch
-  static const lmk::family_fn table[lmk::LMK_NFAMILY][3] = {
-      {lmk::launch_f0p0, lmk::launch_f0p1, lmk::launch_f0p2}, {nullptr, nullptr, nullptr},
-      {lmk::launch_f2p0, lmk::launch_f2p1, lmk::launch_f2p2}, {nullptr, nullptr, nullptr},
-      {lmk::launch_f4p0, lmk::launch_f4p1, lmk::launch_f4p2}, {lmk::launch_f5p0, lmk::launch_f5p1, lmk::launch_f5p2},
-      {lmk::launch_f6p0, lmk::launch_f6p1, lmk::launch_f6p2}, {lmk::launch_f7p0, lmk::launch_f7p1, lmk::launch_f7p2},
-      {lmk::launch_f8p0, lmk::launch_f8p1, lmk::launch_f8p2}, {lmk::launch_f9p0, lmk::launch_f9p1, lmk::launch_f9p2},
-      {lmk::launch_f10p0, lmk::launch_f10p1, lmk::launch_f10p2}, {lmk::launch_f11p0, lmk::launch_f11p1, lmk::launch_f11p2}};
+  const auto& table = kFamilyTable;
   const int fam = family_of(b);
   if (fam < 0) { g_launch_err = "chains of six links are compiled for Euler, of seven links for RK4 — condim-3 pyramids, no muscles only"; return; }
-  const LaunchCtx L = {b->stream, b->n_active, b->epb};
+  const LaunchCtx L = {b->stream, b->n_active, b->epb, b->m->lds_limit, &g_launch_err, nullptr, 0};
   if (b->n_active <= 0) return;            // an empty active list: nothing to run
+  if (b->lds_ok[FWD] != b->epb) {          // (lm_batch_set_layout refuses such a layout; a model's default layout and the forward kernel are checked here, once)
+    g_layout_err = layout_refusal(b, b->epb, FWD);
+    if (!g_layout_err.empty()) { g_launch_err = g_layout_err.c_str(); return; }
+    b->lds_ok[FWD] = b->epb;
+  }
   if (fam == 6) {
     if (b->m->T.na > 0) { g_launch_err = "muscle models need the <5 links, <=4 contacts per chain, Euler> family"; return; }
     if (b->dofprm) { g_launch_err = "per-environment joint parameters are not compiled for this model family"; return; }
@@ -182,8 +237,9 @@ static void launch_variant(lm_batch* b, const KArgs& a) {
       // while the previous launch tails off and wait for its drain pass on the device). Without this a host that queues hundreds of
       // launches ahead of the device would start them long before their launch: they would wait out their time-out and leave
       if (b->epoch >= 2 && hipStreamWaitEvent(b->stream2, b->ev_done[b->epoch & 1], 0) != hipSuccess) { g_launch_err = "stream wait failed"; return; }
-      const LaunchCtx L2 = {b->stream2, b->N, want};
+      const LaunchCtx L2 = {b->stream2, b->N, want, b->m->lds_limit, &g_launch_err, nullptr, 0};
       if (!table[fam][0](L2, p, big) && !table[fam][1](L2, p, big) && !table[fam][2](L2, p, big)) { g_launch_err = "no replay kernel in the family"; return; }
+      if (g_launch_err) return;              // (launch_one refused: nothing is in flight)
       if (hipEventRecord(b->ev_join, b->stream2) != hipSuccess) { g_launch_err = "stream join failed"; return; }
       pollers = true;
 
@@ -201,13 +257,15 @@ static void launch_variant(lm_batch* b, const KArgs& a) {
     }
   };
   if (!table[fam][0](L, r, kind) && !table[fam][1](L, r, kind) && !table[fam][2](L, r, kind)) { bail("no kernel of this kind in the family"); return; }
+  if (g_launch_err) { bail(g_launch_err); return; }
   if (replay) {
     // the drain pass, behind the regular launch AND the pollers: whatever is still listed; resets the control words. An empty
     // list costs a few microseconds (its workgroups read a word and leave)
     if (pollers && hipStreamWaitEvent(b->stream, b->ev_join, 0) != hipSuccess) { bail("stream join failed"); return; }
     r.drain = 1; r.stats_off = 0;
-    const LaunchCtx L3 = {b->stream, b->N, lmk::kReplayGrid};
+    const LaunchCtx L3 = {b->stream, b->N, lmk::kReplayGrid, b->m->lds_limit, &g_launch_err, nullptr, 0};
     if (!table[fam][0](L3, r, big) && !table[fam][1](L3, r, big) && !table[fam][2](L3, r, big)) { bail("no replay kernel in the family"); return; }
+    if (g_launch_err) { bail(g_launch_err); return; }
     if (hipEventRecord(b->ev_done[b->epoch & 1], b->stream) != hipSuccess) { bail("event record failed"); return; }
     b->epoch++;
   }
@@ -239,6 +297,14 @@ int lm_model_create(const double* cmod, size_t n, int device, lm_model** out) {
   std::unique_ptr<lm_model, void (*)(lm_model*)> guard(new lm_model(), lm_model_destroy);      // freed on every error path
   lm_model* m = guard.get();
   m->device = device;
+  {
+    // the LDS one workgroup may take. A runtime that reports no more than the 64 KB every launch gets without opting in says nothing
+    // about the CU: then the 160 KB of a CDNA4 CU that lm_core.h's LaneMem budgets with
+    int per_block = 0;
+    if (hipDeviceGetAttribute(&per_block, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess) per_block = 0;
+    m->lds_reported = per_block > 64 * 1024;
+    m->lds_limit = m->lds_reported ? (size_t)per_block : kLdsAssumed;
+  }
   std::vector<float> cm(LM_CM_SIZE);
   for (int i = 0; i < LM_CM_SIZE; i++) cm[i] = (float)cmod[LM_HEADER_SIZE + i];
   if (LM_PROBE_ENV("LM_NO_PAIRS")) for (int c = 0; c < LM_NCHAIN; c++) cm[LM_CM_CHAINS + LM_C_NLPAIR * LM_NCHAIN + c] = 0.0f;      // A/B: self-collision broad phase off
@@ -505,6 +571,9 @@ int lm_batch_set_layout(lm_batch* b, int envs_per_workgroup) {
   if (envs_per_workgroup == 4) envs_per_workgroup = def;      // the advertised default, also for a batch of fewer than four environments
   if (envs_per_workgroup != def && envs_per_workgroup != 8 && envs_per_workgroup != 16) return fail("environments per workgroup: 4 (replicated layout), 8 or 16 (plain layout)");
   if (envs_per_workgroup > def && !family_has_replicas(b)) return fail("the generic kernel family has one layout only");
+  // a layout whose kernels ask for more LDS than a CU has is refused HERE, with the byte counts, before anything is launched (the
+  // muscle humanoid with pair tables at 16: 169 048 B against 163 840 B — launched, that ended in an illegal memory access)
+  { const std::string why = layout_refusal(b, envs_per_workgroup, false); if (!why.empty()) return fail(why); }
   b->epb = envs_per_workgroup;
   b->nblocks = (b->N + b->epb - 1) / b->epb;
   return 0;
@@ -974,6 +1043,14 @@ int lm_batch_set_active(lm_batch* b, const int32_t* env_ids, int count) {
 #define LM_TOOLCHAIN "unknown (built outside csrc/Makefile)"
 #endif
 const char* lm_toolchain(void) { return LM_TOOLCHAIN; }
+
+int lm_lds_bytes(int family, int kind, int envs_per_workgroup, int cm_used_floats, int* static_bytes, int* dynamic_bytes) {
+  lmk::LdsUse u;
+  if (kind < 0 || kind >= lmk::LMK_NKINDS || cm_used_floats < 0 || !lds_of(family, kind, envs_per_workgroup, cm_used_floats, LM_MAXC, &u)) return fail("no kernel of that family and kind");
+  if (static_bytes) *static_bytes = (int)u.stat;
+  if (dynamic_bytes) *dynamic_bytes = (int)u.dyn;
+  return 0;
+}
 
 int lm_step(lm_batch* b, const float* action, float* obs, float* reward, uint8_t* done) {
   HIPCHK(hipSetDevice(b->m->device));

@@ -805,7 +805,15 @@ __global__ __launch_bounds__(64) void step_kernel(KArgs a) {
 }
 
 // ---- launch helpers ---------------------------------------------------------------------------------------------
-struct LaunchCtx { hipStream_t stream; int N, epb; };
+// LDS of one launch in bytes: what the kernel declares itself (`stat`: the muscle table of the muscle families and the statistics block)
+// and what the launch asks for (`dyn`: the model's constant table + lane memory)
+struct LdsUse { size_t stat, dyn; };
+// `stat_bytes`: the kernel's static LDS (launch_family / lm_family.hip fill it in from the family's NM); `lds_limit`: what one CU holds;
+// `err`: where a refused launch leaves its reason (lm_kernels.hip: g_launch_err); `probe`: not null = launch NOTHING, report the LDS the
+// launch would take (lm_kernels.hip: lds_of — the same code path as the launch, so the two cannot disagree)
+struct LaunchCtx { hipStream_t stream; int N, epb; size_t lds_limit; const char** err; LdsUse* probe; size_t stat_bytes; };
+// static LDS of step_kernel<..., NM, ...>: `mt` and `blk_stats` (both float arrays: no padding between them or in front of the dynamic part)
+constexpr size_t static_lds_bytes(int nm) { return sizeof(float) * ((size_t)(nm > 0 ? LM_MT_SIZE : 1) + kNStats); }
 
 // kernel kinds of one family (picked by the host, lm_kernels.hip::launch_variant)
 enum { LMK_FWD = 0, LMK_REP4, LMK_REP1, LMK_DR_REP4, LMK_DR_REP1, LMK_FUSED, LMK_FUSED_DR, LMK_DRV_REP4, LMK_DRV_REP1, LMK_FUSED_DRV,
@@ -824,12 +832,30 @@ constexpr int kReplayRep = LM_REPLAY_REP;
 constexpr int kReplayGrid = 128;    // workgroups of the replay kernel's drain pass (each walks the list with this stride), and the most pollers
 constexpr int kPollMul = 2, kPollAdd = 2, kPollCap = 32;      // pollers of a launch = kPollMul / 2 x (recently abandoned steps) + kPollAdd, at most kPollCap (lm_kernels.hip)
 
+// a launch that is not made leaves its reason in *L.err (one buffer per thread, like lm_last_error's)
+static void launch_refused(const LaunchCtx& L, const char* fmt, size_t v0, size_t v1, size_t v2, size_t v3) {
+  static thread_local char why[256];
+  snprintf(why, sizeof(why), fmt, v0, v1, v2, v3);
+  if (L.err) *L.err = why;
+}
+// never ask a CU for more LDS than it has — the static part included, which hipFuncAttributeMaxDynamicSharedMemorySize does not see
+// (HumanoidMuscle with pair tables at 16 environments per workgroup: 13 400 B static + 155 648 B dynamic against 163 840 B; that launch
+// was made, and ended in an illegal memory access)
+static bool lds_fits(const LaunchCtx& L, size_t dyn_bytes) {
+  if (L.stat_bytes + dyn_bytes <= L.lds_limit) return true;
+  launch_refused(L, "the kernel needs %zu B of LDS per workgroup (%zu B static + %zu B dynamic), a compute unit has %zu B", L.stat_bytes + dyn_bytes, L.stat_bytes, dyn_bytes, L.lds_limit);
+  return false;
+}
+
 template <class K>
 static void launch_one(K kernel, dim3 grid, dim3 block, size_t lane_floats, const LaunchCtx& L, const KArgs& a) {
   // the workgroup's LDS = constant table (the part the model uses) + lane memory, both dynamic; opt in to more than
   // the default 64 KB cap
   const size_t bytes = sizeof(float) * ((size_t)a.T.cm_used + lane_floats);
-  hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (L.probe) { L.probe->stat = L.stat_bytes; L.probe->dyn = bytes; return; }
+  if (!lds_fits(L, bytes)) return;
+  const hipError_t rc = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (rc != hipSuccess) { launch_refused(L, "hipFuncSetAttribute(MaxDynamicSharedMemorySize = %zu B) failed: error %zu", bytes, (size_t)rc, 0, 0); return; }
   hipLaunchKernelGGL(kernel, grid, block, bytes, L.stream, a);
 }
 
@@ -843,7 +869,9 @@ static void launch_term(K kernel, KT kernel_term, dim3 grid, dim3 block, size_t 
 // one robot family = (links per chain MC, contact slots per chain NS, integrator, compiled-in cone, muscles per chain NM, pair
 // pass PM of the regular kernels: 0 none, 1 with the convex collider, 2 without — the replay kernel has it)
 template <int MC, int NS, bool RK4, int CONE, int NM, int PART, int PM = 0>
-static bool launch_family(const LaunchCtx& L, const KArgs& a, int kind) {
+static bool launch_family(const LaunchCtx& L0, const KArgs& a, int kind) {
+  LaunchCtx L = L0;
+  L.stat_bytes = static_lds_bytes(NM);
   const dim3 grid((L.N + L.epb - 1) / L.epb);
   using LMm = lm::LaneMemFor<MC, NS, NM, (PM == 1 || PM == 2), CONE>;       // (as the kernel's own alias: detection-only kernels carry no pair extension)
   const size_t plain = (size_t)LMm::kGroup * ((4 * L.epb + 15) / 16), rep = (size_t)LMm::kGroup;

@@ -115,7 +115,8 @@ def _check_twin(env, steps, n, ngrf=0):
 
 @pytest.mark.parametrize("task,n,kw", [("UnitreeA1.simple", 37, {}), ("HumanoidTorque.run", 64, {}), ("HumanoidMuscle.run", 64, {}),
                                        ("HumanoidTorque.walk", 64, dict(foot_forces=True)),
-                                       ("UnitreeA1.simple", 37, dict(replay=2)), ("UnitreeA1.simple", 37, dict(layout=16))])
+                                       ("UnitreeA1.simple", 37, dict(replay=2)), ("UnitreeA1.simple", 37, dict(layout=16)),
+                                       ("HumanoidTorque.run", 64, dict(layout=16))])
 def test_terminal_row_is_the_twin_batchs_observation_bitwise(task, n, kw):
     """At the first step in which A's done byte has bit 1, A's terminal row equals the observation of the twin that did not restart,
     bit for bit: dataset rows (n = 37: a ragged last workgroup) of which twelve leave a termination bound in the first step, the others
