@@ -39,6 +39,9 @@
  *                          inside (action repeat / frame skip, K-step action chunks, sampling planners, open-loop replay of
  *                          recorded actions), with every step's observation, reward and done byte recorded
  *   lm_forward_debug    <- mujoco.mj_forward (base.py:362) with intermediate results, for parity tests
+ *   lm_snapshot_create / _save / _restore / _export / _import <- copy.copy(data) / mujoco.mj_copyData of every environment's MjData
+ *                          (the reference keeps one MjData per environment on the host, base.py:185; it has no call of its own for
+ *                          this): save, rewind and fork environments on the device, for sampling planners and checkpoints
  *
  * All arrays at the boundary are caller-owned HOST buffers, row-major [n_envs][dim], float32.
  * Device memory lives behind the opaque handles. Functions return 0 on success, non-zero on error;
@@ -133,7 +136,7 @@ int lm_set_state(lm_batch* b, const float* qpos, const float* qvel, const uint8_
 int lm_get_state(lm_batch* b, float* qpos, float* qvel);
 int lm_set_goal(lm_batch* b, const float* goal, const uint8_t* mask);
 /* muscle activations [n_envs][na] (data.act of the reference: mj_resetData zeroes it, base.py:180, so lm_set_state
-   and device-side episode restarts zero it too; these two exist for checkpointing and for parity tests) */
+   and device-side episode restarts zero it too; these two exist for parity tests and for single arrays; a CHECKPOINT is lm_snapshot_save / lm_snapshot_export) */
 /* per-environment joint damping / stiffness / frictionloss [n_envs][nv] (NULL = leave as is) — what the reference's
    domain randomisation changes per episode by re-compiling the model (utils/domain_randomization.py:299-383,
    base.py:183-185). The first call allocates the arrays (initialised with the model's values) and switches the batch
@@ -286,6 +289,50 @@ int lm_rollout_fused(lm_batch* b, int n_steps, int steps_per_launch, int action_
    into *stats (kernel_ms: this call's, by HIP events); with sync = 0 *stats is not written. */
 int lm_rollout_tape(lm_batch* b, int n_steps, int steps_per_launch, const float* d_actions, long long action_step_stride,
                     float* d_obs, float* d_reward, uint8_t* d_done, float* d_term, void* stream, int sync, lm_stats* stats);
+
+/* SNAPSHOTS: the state of every environment of a batch, kept in device memory — save, rewind, fork (environment e continues from
+   the state environment w reached), and a self-describing blob for files. A restored batch continues BIT FOR BIT as the batch that
+   was saved would have (lm_set_state cannot do that: it carries qpos / qvel only and clears the rest).
+   A snapshot holds everything a later control step reads, per environment: qpos, qvel, the solver warm start, the goal, the muscle
+   activations, the episode's step and the episode count, the replay prediction mark, the self-collision slack, the convex collider's
+   warm-start cache, the per-environment joint parameters (when allocated), the model-variant index — with the model compiler instead
+   the environment's own slot of the inertial record / geom table / geom-pair table, its restart flag, draw counter and draws — the
+   batch's last-step rows (observation, reward, done byte, validity flags), and the batch's count of control steps.
+   It does NOT hold settings (the reset table, seed and horizon, the active list, the layout, the replay mode, the randomisation
+   spec, the variant pool, the compiler program), accumulators and diagnostics (lm_stats, replay marks, the pollers' hint, timers),
+   output buffers (the pinned ring, terminal-observation buffers of the library or the caller) or the scratch of a launch (the
+   replay list and its control words, the resume states): every launch leaves those consumed.
+     lm_snapshot_create   device storage sized for b's configuration NOW: n_envs, nv, na, nobs, the collider cache's pairs, whether
+                          joint parameters exist, the number of variants and their pair floats, the model compiler and its draws.
+                          Save, restore and import refuse a batch whose configuration differs, naming the field; nothing is launched.
+                          flags bit 0: leave the convex collider's warm-start cache out (HumanoidTorque: 88 KB per environment,
+                          363 MB at 4096). Restore then leaves the batch's cache rows as they are. The cache is meant to decide how
+                          fast the collider answers, not what; equal supports on flat hull faces may break that, so only the default
+                          (cache kept) is promised bitwise.
+     lm_snapshot_save     one kernel launch copies every state array into the snapshot (again: into the same storage).
+     lm_snapshot_restore  one launch back. d_src NULL: every environment takes its own saved state, and the batch's count of control
+                          steps is rewound to the saved one. Otherwise d_src is a DEVICE int32 [n_envs]: environment e takes the saved
+                          state of environment d_src[e]; an entry outside [0, n_envs) means "e keeps what it has" (nothing is read or
+                          written for e), and the count of control steps is left alone.
+                          FORK: the copy includes the episode's step and the episode count, while every random number stays keyed by the
+                          global environment id. A forked environment equals its source until one of them restarts on the device; from
+                          then on each draws its own reset row (and model).
+     lm_snapshot_bytes    device bytes of the snapshot
+     lm_snapshot_export / _import  the snapshot <-> a host blob of `n` bytes: a header (magic word, version, the configuration, the
+                          flags, the count of control steps; 64 bytes) and lm_snapshot_bytes of payload. Import refuses a blob that is
+                          short, foreign or of another configuration and leaves snapshot and batch as they were. Synchronous.
+   `stream`, `sync`: as in lm_rollout_tape. The copy is ordered behind everything the batch has in flight — the library's stream, the
+   replay kernel's pollers, a launch that lm_step_device queued on a caller's stream with sync = 0 — and the library's stream behind
+   the copy. With sync = 0 nothing waits on the host: a planner saves, rolls a tape, picks winners on the device and restores with
+   d_src without a synchronisation. The snapshot must outlive the work queued on it (lm_snapshot_destroy waits for the device). */
+typedef struct lm_snapshot lm_snapshot;
+int lm_snapshot_create(lm_batch* b, int flags, lm_snapshot** out);
+void lm_snapshot_destroy(lm_snapshot* s);
+int lm_snapshot_save(lm_batch* b, lm_snapshot* s, void* stream, int sync);
+int lm_snapshot_restore(lm_batch* b, const lm_snapshot* s, const int32_t* d_src, void* stream, int sync);
+long long lm_snapshot_bytes(const lm_snapshot* s);
+int lm_snapshot_export(lm_batch* b, const lm_snapshot* s, void* host, long long n);
+int lm_snapshot_import(lm_batch* b, lm_snapshot* s, const void* host, long long n);
 
 /* Validity flags of the LAST control step, one byte per environment: 1 = a contact was dropped (the chain's contact slots were
  * full), 2 = two geoms of the robot WITHOUT a pair collider (a box or cylinder against another geom) came within the contact

@@ -41,7 +41,9 @@ EXPORTS = ["lm_device_count", "lm_last_error", "lm_toolchain", "lm_lds_bytes", "
            "lm_set_terminal_obs", "lm_get_terminal_obs", "lm_pinned_terminal_obs",
            "lm_set_reset_table", "lm_set_auto_reset", "lm_rollout", "lm_rollout_fused", "lm_rollout_tape", "lm_forward_debug", "lm_get_stats", "lm_sync",
            "lm_get_flags", "lm_set_model_variants", "lm_set_variant_index", "lm_get_variant_index", "lm_set_variant_rows",
-           "lm_set_model_compiler", "lm_compile_models", "lm_get_model_draws", "lm_get_model_tables"]
+           "lm_set_model_compiler", "lm_compile_models", "lm_get_model_draws", "lm_get_model_tables",
+           "lm_snapshot_create", "lm_snapshot_destroy", "lm_snapshot_save", "lm_snapshot_restore", "lm_snapshot_bytes",
+           "lm_snapshot_export", "lm_snapshot_import"]
 
 _lib = None
 
@@ -109,6 +111,15 @@ def load_library():
     lib.lm_compile_models.argtypes = [C.c_void_p, _U8]
     lib.lm_get_model_draws.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
     lib.lm_get_model_tables.argtypes = [C.c_void_p, C.c_int, _F, _F, _F]
+    lib.lm_snapshot_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+    lib.lm_snapshot_destroy.argtypes = [C.c_void_p]
+    lib.lm_snapshot_destroy.restype = None
+    lib.lm_snapshot_save.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    lib.lm_snapshot_restore.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    lib.lm_snapshot_bytes.argtypes = [C.c_void_p]
+    lib.lm_snapshot_bytes.restype = C.c_longlong
+    lib.lm_snapshot_export.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong]
+    lib.lm_snapshot_import.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong]
     _lib = lib
     return lib
 
@@ -197,8 +208,57 @@ def check_tape_args(n, nu, nobs, actions, obs=None, reward=None, done=None, term
     return T, stride, spl
 
 
+SNAPSHOT_BLOB_HEADER = 64          # bytes in front of the payload of lm_snapshot_export (include/locohip.h)
+
+
+def check_restore_args(n, src=None, mask=None, snapshot=None, batch=None):
+    """The argument checks of :meth:`HipBatch.restore` / :meth:`HipBatch.fork`, without a device. ``src``: None, an object with
+    ``data_ptr()`` (a torch tensor: int32, [n], contiguous, on the device) or integers on the host (numpy array / list, [n]); ``mask``:
+    booleans [n], sugar for ``src[e] = e if mask[e] else -1``; not both. ``snapshot`` (with ``batch``): an open snapshot of THIS batch,
+    taken under the batch's present configuration. Returns ``(kind, value)``: ``("all", None)``, ``("device", tensor)``,
+    ``("host", int32 array)`` — entries outside [0, n) folded to -1 — or ``("device_mask", tensor)``. Raises ValueError."""
+    if snapshot is not None:
+        if getattr(snapshot, "closed", False):
+            raise ValueError("restore: the snapshot is closed (its batch was closed, or close() was called)")
+        if batch is not None and getattr(snapshot, "batch", None) is not batch:
+            raise ValueError("restore: the snapshot belongs to another batch")
+        if batch is not None and tuple(snapshot.signature) != tuple(batch.snapshot_signature()):
+            raise ValueError("restore: the snapshot was taken under another configuration of the batch: %s, now %s"
+                             % (tuple(snapshot.signature), tuple(batch.snapshot_signature())))
+    if src is not None and mask is not None:
+        raise ValueError("restore: give src or mask, not both")
+    if src is None and mask is None:
+        return "all", None
+    name, x = ("src", src) if src is not None else ("mask", mask)
+    if hasattr(x, "data_ptr"):
+        if tuple(x.shape) != (n,):
+            raise ValueError("restore: %s must be [%d], not %s" % (name, n, list(x.shape)))
+        want = "int32" if src is not None else "bool"
+        if want not in str(x.dtype):
+            raise ValueError("restore: a %s tensor must be %s, not %s" % (name, want, x.dtype))
+        if not x.is_contiguous():
+            raise ValueError("restore: %s must be contiguous" % name)
+        if hasattr(x, "is_cuda") and not x.is_cuda:
+            raise ValueError("restore: a %s tensor must live on the device (host values: a numpy array or a list)" % name)
+        return ("device" if src is not None else "device_mask"), x
+    if isinstance(x, (str, bytes)) or np.ndim(x) == 0:
+        raise ValueError("restore: %s must be a sequence of %d entries, not %s" % (name, n, type(x).__name__))
+    a = np.asarray(x)
+    if a.shape != (n,):
+        raise ValueError("restore: %s must be [%d], not %s" % (name, n, list(a.shape)))
+    if src is not None:
+        if a.dtype.kind not in "iu":
+            raise ValueError("restore: src must hold integers, not %s" % a.dtype)
+        a = a.astype(np.int64)
+        return "host", np.ascontiguousarray(np.where((a < 0) | (a >= n), -1, a), dtype=np.int32)
+    if a.dtype.kind != "b":
+        raise ValueError("restore: mask must hold booleans, not %s" % a.dtype)
+    return "host", np.ascontiguousarray(np.where(a, np.arange(n), -1), dtype=np.int32)
+
+
 class HipModel:
     def __init__(self, chain_model, device=0):
+        self.device = int(device)
         lib = load_library()
         if lib.lm_device_count() <= 0:
             raise BackendError("no HIP device visible: the batched simulator needs an MI355X (no CPU fallback)")
@@ -219,6 +279,51 @@ class HipModel:
     __del__ = close
 
 
+class Snapshot:
+    """The state of every environment of a :class:`HipBatch`, in device memory (``lm_snapshot_*``). Made by
+    :meth:`HipBatch.snapshot`; holds a reference to its batch, whose ``close()`` closes it."""
+
+    def __init__(self, batch, keep_collider_cache=True):
+        self.batch = batch
+        self._lib = batch._lib
+        self._h = None
+        self.keep_collider_cache = bool(keep_collider_cache)
+        self.signature = batch.snapshot_signature()
+        h = C.c_void_p()
+        _check(self._lib.lm_snapshot_create(batch._h, 0 if keep_collider_cache else 1, C.byref(h)))
+        self._h = h
+        batch._snapshots.add(self)
+
+    @property
+    def closed(self):
+        return self._h is None
+
+    @property
+    def nbytes(self):
+        return int(self._lib.lm_snapshot_bytes(self._h)) if self._h else 0
+
+    def save(self, stream=None, sync=True):
+        """Save the batch's present state into this snapshot's storage (one kernel launch)."""
+        check_restore_args(self.batch.n, snapshot=self, batch=self.batch)
+        _check(self._lib.lm_snapshot_save(self.batch._h, self._h, None if stream is None else C.c_void_p(int(stream)), int(bool(sync))))
+        return self
+
+    def to_bytes(self):
+        """The snapshot as a self-describing blob (``lm_snapshot_export``), for files; :meth:`HipBatch.snapshot_from_bytes` reads it."""
+        if self.closed:
+            raise ValueError("to_bytes: the snapshot is closed")
+        buf = np.empty(SNAPSHOT_BLOB_HEADER + self.nbytes, dtype=np.uint8)
+        _check(self._lib.lm_snapshot_export(self.batch._h, self._h, C.c_void_p(buf.ctypes.data), len(buf)))
+        return buf.tobytes()
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.lm_snapshot_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+
 class HipBatch:
     """A batch of ``n_envs`` lock-step environments resident on one GPU."""
 
@@ -227,6 +332,9 @@ class HipBatch:
         self.model = model
         self.n = int(n_envs)
         self._lib = load_library()
+        import weakref
+        self._snapshots = weakref.WeakSet()
+        self._fork_snapshot = self._src_keep = None
         h = C.c_void_p()
         _check(self._lib.lm_batch_create(model._h, self.n, C.byref(h)))
         self._h = h
@@ -237,6 +345,9 @@ class HipBatch:
         self.na = d.na
 
     def close(self):
+        for snap in list(getattr(self, "_snapshots", ())):      # the batch's snapshots die with it (their storage first)
+            snap.close()
+        self._fork_snapshot = self._src_keep = None
         if getattr(self, "_h", None):
             self._lib.lm_batch_destroy(self._h)
             self._h = None
@@ -314,6 +425,7 @@ class HipBatch:
         if not tables:
             _check(self._lib.lm_set_model_variants(self._h, None, None, None, 0, 0))
             self.n_variants = 0
+            self._compiler_on = False
             return
         rec = np.ascontiguousarray(np.stack([t[0] for t in tables]), dtype=np.float32)
         gt = np.ascontiguousarray(np.stack([t[1] for t in tables]), dtype=np.float32)
@@ -321,6 +433,7 @@ class HipBatch:
         gpt = np.ascontiguousarray(np.stack([t[2] for t in tables]), dtype=np.float32) if npair else None
         _check(self._lib.lm_set_model_variants(self._h, _fp(rec), _fp(gt), _fp(gpt) if gpt is not None else None, npair, len(tables)))
         self.n_variants = len(tables)
+        self._compiler_on = False
 
     def set_model_compiler(self, program, nominal_tables, seed=0):
         """The model compiler on the device: ``program`` = (int32, float64) of ``lowering.model_compiler_tables``, ``nominal_tables`` =
@@ -350,6 +463,7 @@ class HipBatch:
         _check(self._lib.lm_set_model_compiler(self._h, ib.ctypes.data_as(C.POINTER(C.c_int32)), len(ib), db.ctypes.data_as(C.POINTER(C.c_double)),
                                                len(db), _fp(rec), _fp(gt), _fp(gpt) if gpt is not None else None, npair, int(seed) & (2 ** 64 - 1)))
         self.n_variants = self.n
+        self._compiler_on = True
         self.n_model_draws = int(ib[4])
         self._table_sizes = (len(rec), len(gt), npair)
 
@@ -544,6 +658,74 @@ class HipBatch:
         _check(self._lib.lm_rollout_tape(self._h, T, spl, ptr(actions), stride, ptr(obs), ptr(reward), ptr(done), ptr(terminal),
                                          None if stream is None else C.c_void_p(int(stream)), int(bool(sync)), C.byref(st) if sync else None))
         return st.as_dict() if sync else None
+
+    # ---- snapshots (include/locohip.h lm_snapshot_*)
+    def snapshot_signature(self):
+        """What a snapshot must agree on with the batch, as far as this layer knows it (the library compares its own, fuller list —
+        the joint-parameter arrays and the collider cache among it — and refuses with the field's name)."""
+        compiler = getattr(self, "n_model_draws", 0) if getattr(self, "_compiler_on", False) else 0
+        return (self.n, self.nv, self.na, self.nobs, int(getattr(self, "n_variants", 0)), int(compiler))
+
+    def snapshot(self, keep_collider_cache=True, stream=None, sync=True):
+        """Save the state of every environment on the device and return the :class:`Snapshot`: everything a later control step reads,
+        so that :meth:`restore` continues bit for bit. ``keep_collider_cache=False`` leaves the convex collider's warm-start cache out
+        (88 KB per HumanoidTorque environment); only the default is promised bitwise."""
+        return Snapshot(self, keep_collider_cache).save(stream=stream, sync=sync)
+
+    def restore(self, snap, src=None, stream=None, sync=True, mask=None):
+        """Put the batch back to ``snap``. ``src`` None: every environment takes its own saved state, and the count of control steps
+        is rewound. Otherwise environment e takes the saved state of environment ``src[e]`` — an int32 CUDA tensor [n] (nothing is
+        copied, nothing waits with ``sync=False``), or a numpy array / list of ints, which is uploaded; entries outside [0, n) mean
+        "keep what it has". ``mask`` (booleans [n]) is sugar for ``src[e] = e if mask[e] else -1``.
+        A forked environment copies its source's episode step and episode count, but random numbers stay keyed by the environment's
+        own id: it equals its source until one of them restarts on the device."""
+        kind, val = check_restore_args(self.n, src, mask, snapshot=snap, batch=self)
+        ptr = None
+        if kind != "all":
+            import torch
+            if kind == "host":
+                val = torch.from_numpy(val).to(torch.device("cuda", self.model.device))      # (blocking: on the device when it returns)
+            elif kind == "device_mask":
+                ids = torch.arange(self.n, dtype=torch.int32, device=val.device)
+                val = torch.where(val, ids, torch.full_like(ids, -1))
+                if stream is None or int(stream) != int(torch.cuda.current_stream(val.device).cuda_stream):
+                    torch.cuda.current_stream(val.device).synchronize()                          # made on torch's stream, read on another
+            self._src_keep = val          # alive until the next restore: with sync=False the copy may still be queued
+            ptr = C.c_void_p(int(val.data_ptr()))
+        _check(self._lib.lm_snapshot_restore(self._h, snap._h, ptr, None if stream is None else C.c_void_p(int(stream)), int(bool(sync))))
+
+    def fork(self, src=None, stream=None, sync=True, mask=None):
+        """Environment e continues from the PRESENT state of environment ``src[e]``: a save into a scratch snapshot owned by the batch,
+        then :meth:`restore` with ``src`` (same forms, same ``mask``)."""
+        check_restore_args(self.n, src, mask)
+        snap = self._fork_snapshot
+        if snap is None or snap.closed or tuple(snap.signature) != tuple(self.snapshot_signature()):
+            if snap is not None:
+                snap.close()
+            snap = self._fork_snapshot = Snapshot(self)
+        try:
+            snap.save(stream=stream, sync=False)
+        except BackendError:
+            # the library's configuration changed where this layer does not see it (joint parameters allocated since): a fresh scratch
+            snap.close()
+            snap = self._fork_snapshot = Snapshot(self)
+            snap.save(stream=stream, sync=False)
+        self.restore(snap, src=src, stream=stream, sync=sync, mask=mask)
+
+    def snapshot_from_bytes(self, blob):
+        """A :class:`Snapshot` of THIS batch filled from ``Snapshot.to_bytes()`` of a batch of the same configuration. A blob that is
+        cut short, foreign or of another configuration is refused (BackendError) and nothing changes."""
+        buf = np.frombuffer(bytes(blob), dtype=np.uint8)
+        keep = True
+        if len(buf) >= SNAPSHOT_BLOB_HEADER:
+            keep = not (int(np.frombuffer(buf[48:52].tobytes(), dtype=np.int32)[0]) & 1)      # the header's flags word
+        snap = Snapshot(self, keep_collider_cache=keep)
+        try:
+            _check(self._lib.lm_snapshot_import(self._h, snap._h, C.c_void_p(buf.ctypes.data), len(buf)))
+        except BackendError:
+            snap.close()
+            raise
+        return snap
 
     def forward_debug(self, action):
         a = _f32(action, (self.n, self.nu))

@@ -3,6 +3,7 @@
 // lm_family.hip (one object per family and part, so the library builds in parallel).
 #include "lm_step.h"
 #include "lm_compile.h"
+#include "lm_snapshot.h"
 #include <memory>
 
 using lmk::KArgs; using lmk::Task; using lmk::DevStats; using lmk::LaunchCtx;
@@ -1445,6 +1446,177 @@ int lm_debug_mpr_counters(lm_batch* b, unsigned long long* out8 /* 16 values */)
 }
 
 #endif
+
+// ---- snapshots (include/locohip.h lm_snapshot_*; the table, the walks and the kernel: lm_snapshot.h)
+}  // extern "C"
+
+struct lm_snapshot {
+  int sig[10];               // the configuration it was created for (kSnapSigNames)
+  int flags;                 // bit 0: no collider cache
+  int device;
+  long long bytes;           // device storage
+  unsigned char* data;
+  unsigned step_index;       // the batch's count of control steps at the save
+  bool saved;
+};
+
+static const char* const kSnapSigNames[10] = {"n_envs", "nv", "na", "nobs", "mprc_pairs", "dof_params", "n_variants", "gpt_floats", "model_compiler", "n_model_draws"};
+constexpr uint32_t kSnapMagic = 0x50534d4cu /* "LMSP" */, kSnapVersion = 1;
+struct SnapBlobHead { uint32_t magic, version; int32_t sig[10]; int32_t flags; uint32_t step_index; int64_t bytes; };
+
+static void snap_signature(const lm_batch* b, int* sig) {
+  const Task& T = b->m->T;
+  const int v[10] = {b->N, T.nv, T.na, T.nobs, b->mprc_pairs, b->dofprm ? 1 : 0, b->nvar, b->gpt_floats, b->mc_ib ? 1 : 0, b->mc_ib ? b->mc_ndraw : 0};
+  for (int i = 0; i < 10; i++) sig[i] = v[i];
+}
+
+// the batch's state arrays in the snapshot's order: a function of the signature and the flags alone, so that a snapshot created for
+// one batch fits every batch of the same signature (lm_snapshot_import into a fresh batch)
+static bool snap_table(const lm_batch* b, int flags, lms::Table* t) {
+  const Task& T = b->m->T;
+  const int N = b->N;
+  lms::table_init(t, N);
+  bool ok = lms::table_add_soa(t, b->qpos, T.nv, 4) && lms::table_add_soa(t, b->qvel, T.nv, 4) && lms::table_add_soa(t, b->warm, T.nv, 4) &&
+            lms::table_add_soa(t, b->goal, 4, 4) && lms::table_add_soa(t, b->slack, 12, 4) && lms::table_add_soa(t, b->ep_step, 1, 4) &&
+            lms::table_add_soa(t, b->ep_count, 1, 4) && lms::table_add_soa(t, b->premark, 1, 4) && lms::table_add_soa(t, b->reward, 1, 4) &&
+            lms::table_add_soa(t, b->done, 1, 1) && lms::table_add_soa(t, b->flags, 1, 1) && lms::table_add_aos(t, b->obs, 4ll * T.nobs);
+  if (ok && b->act) ok = lms::table_add_soa(t, b->act, T.na, 4);
+  if (ok && b->dofprm) ok = lms::table_add_soa(t, b->dofprm, 3 * T.nv, 4);
+  if (ok && b->nvar > 0 && !b->mc_ib) ok = lms::table_add_soa(t, b->var, 1, 4);      // a pool: the index is the state, the pool a setting
+  if (ok && b->mc_ib) {
+    // the model compiler: slot e IS environment e's model (var stays the identity), with its restart flag, draw counter and draws
+    ok = lms::table_add_soa(t, b->vdirty, 1, 1) && lms::table_add_soa(t, b->vgen, 1, 4) && lms::table_add_aos(t, b->vdraws, 8ll * b->mc_ndraw) &&
+         lms::table_add_aos(t, b->vrec, 4ll * LM_IR_SIZE * LM_NCHAIN) && lms::table_add_aos(t, b->vgt, 4ll * LM_GT_SIZE);
+    if (ok && b->vgpt) ok = lms::table_add_aos(t, b->vgpt, 4ll * b->gpt_floats);
+  }
+  if (ok && b->mprc && !(flags & 1)) ok = lms::table_add_aos(t, b->mprc, 4ll * lm::kMprCacheFloats * b->mprc_pairs);
+  return ok;
+}
+
+static int snap_check(const lm_batch* b, const int* sig, const char* who, const char* what) {
+  int now[10];
+  snap_signature(b, now);
+  for (int i = 0; i < 10; i++)
+    if (now[i] != sig[i]) {
+      char why[200];
+      snprintf(why, sizeof(why), "%s: the %s is of another configuration: %s = %d, the batch has %d", who, what, kSnapSigNames[i], sig[i], now[i]);
+      return fail(why);
+    }
+  return 0;
+}
+
+// the stream a snapshot operation runs on, ordered behind everything the batch has in flight: the library's own stream (ev_ext, as in
+// lm_rollout_tape), and the last launch with a replay pass wherever it ran — its drain pass waits for the pollers of stream2 (ev_join)
+// and is followed by ev_done, so that event also covers lm_step_device(sync = 0) on ANOTHER caller's stream
+static int snap_enter(lm_batch* b, void* stream, hipStream_t* used_out) {
+  hipStream_t own = b->stream, used = stream ? (hipStream_t)stream : own;
+  if (b->epoch > 0) HIPCHK(hipStreamWaitEvent(used, b->ev_done[(b->epoch - 1) & 1], 0));
+  if (used != own) { HIPCHK(hipEventRecord(b->ev_ext, own)); HIPCHK(hipStreamWaitEvent(used, b->ev_ext, 0)); }
+  *used_out = used;
+  return 0;
+}
+static int snap_leave(lm_batch* b, hipStream_t used, int sync) {
+  HIPCHK(hipGetLastError());
+  if (used != b->stream) { HIPCHK(hipEventRecord(b->ev_ext, used)); HIPCHK(hipStreamWaitEvent(b->stream, b->ev_ext, 0)); }
+  if (sync) HIPCHK(hipStreamSynchronize(used));
+  return 0;
+}
+
+extern "C" {
+
+int lm_snapshot_create(lm_batch* b, int flags, lm_snapshot** out) {
+  if (!b || !out) return fail("lm_snapshot_create: null batch");
+  if (flags & ~1) return fail("lm_snapshot_create: unknown flag bits (bit 0: leave the collider cache out)");
+  HIPCHK(hipSetDevice(b->m->device));
+  lms::Table t;
+  if (!snap_table(b, flags, &t)) return fail("lm_snapshot_create: more state arrays than the segment table holds");
+  std::unique_ptr<lm_snapshot, void (*)(lm_snapshot*)> s(new lm_snapshot(), lm_snapshot_destroy);      // freed on every error path
+  memset(s.get(), 0, sizeof(lm_snapshot));
+  snap_signature(b, s->sig);
+  s->flags = flags; s->device = b->m->device; s->bytes = t.bytes;
+  HIPCHK(hipMalloc(&s->data, (size_t)t.bytes));
+  // (the gaps between segments travel in lm_snapshot_export's blob.) Complete before this returns: the first save may run on a
+  // caller's stream that knows nothing of this one
+  HIPCHK(hipMemsetAsync(s->data, 0, (size_t)t.bytes, b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  *out = s.release();
+  return 0;
+}
+
+void lm_snapshot_destroy(lm_snapshot* s) {
+  if (!s) return;
+  (void)hipSetDevice(s->device);
+  if (s->data) (void)hipFree(s->data);         // (hipFree waits for the device: no copy still runs on it)
+  delete s;
+}
+
+long long lm_snapshot_bytes(const lm_snapshot* s) { return s ? s->bytes : 0; }
+
+int lm_snapshot_save(lm_batch* b, lm_snapshot* s, void* stream, int sync) {
+  if (!b || !s) return fail("lm_snapshot_save: null batch or snapshot");
+  if (snap_check(b, s->sig, "lm_snapshot_save", "snapshot")) return 1;
+  HIPCHK(hipSetDevice(b->m->device));
+  lms::Table t;
+  if (!snap_table(b, s->flags, &t) || t.bytes != s->bytes) return fail("lm_snapshot_save: the snapshot's layout does not match the batch");
+  hipStream_t used;
+  if (snap_enter(b, stream, &used)) return 1;
+  (void)hipGetLastError();
+  lms::launch_copy(t, s->data, nullptr, 0, used);
+  s->step_index = b->step_index; s->saved = true;
+  return snap_leave(b, used, sync);
+}
+
+int lm_snapshot_restore(lm_batch* b, const lm_snapshot* s, const int32_t* d_src, void* stream, int sync) {
+  if (!b || !s) return fail("lm_snapshot_restore: null batch or snapshot");
+  if (!s->saved) return fail("lm_snapshot_restore: nothing was saved into this snapshot");
+  if (snap_check(b, s->sig, "lm_snapshot_restore", "snapshot")) return 1;
+  HIPCHK(hipSetDevice(b->m->device));
+  lms::Table t;
+  if (!snap_table(b, s->flags, &t) || t.bytes != s->bytes) return fail("lm_snapshot_restore: the snapshot's layout does not match the batch");
+  hipStream_t used;
+  if (snap_enter(b, stream, &used)) return 1;
+  (void)hipGetLastError();
+  lms::launch_copy(t, s->data, d_src, 1, used);
+  if (!d_src) b->step_index = s->step_index;      // every environment is back at the save: so is the count that keys the random actions
+  return snap_leave(b, used, sync);
+}
+
+int lm_snapshot_export(lm_batch* b, const lm_snapshot* s, void* host, long long n) {
+  if (!b || !s || !host) return fail("lm_snapshot_export: null argument");
+  if (!s->saved) return fail("lm_snapshot_export: nothing was saved into this snapshot");
+  if (n < (long long)sizeof(SnapBlobHead) + s->bytes) return fail("lm_snapshot_export: the buffer is shorter than the blob (header + lm_snapshot_bytes)");
+  HIPCHK(hipSetDevice(b->m->device));
+  SnapBlobHead h;
+  memset(&h, 0, sizeof(h));
+  h.magic = kSnapMagic; h.version = kSnapVersion; h.flags = s->flags; h.step_index = s->step_index; h.bytes = s->bytes;
+  for (int i = 0; i < 10; i++) h.sig[i] = s->sig[i];
+  memcpy(host, &h, sizeof(h));
+  hipStream_t used;
+  if (snap_enter(b, nullptr, &used)) return 1;
+  HIPCHK(hipMemcpyAsync(static_cast<unsigned char*>(host) + sizeof(h), s->data, (size_t)s->bytes, hipMemcpyDeviceToHost, used));
+  HIPCHK(hipStreamSynchronize(used));
+  return 0;
+}
+
+int lm_snapshot_import(lm_batch* b, lm_snapshot* s, const void* host, long long n) {
+  if (!b || !s || !host) return fail("lm_snapshot_import: null argument");
+  SnapBlobHead h;
+  if (n < (long long)sizeof(h)) return fail("lm_snapshot_import: the blob is shorter than its header");
+  memcpy(&h, host, sizeof(h));
+  if (h.magic != kSnapMagic) return fail("lm_snapshot_import: not a snapshot blob (magic word)");
+  if (h.version != kSnapVersion) return fail("lm_snapshot_import: a blob of another version");
+  if (snap_check(b, h.sig, "lm_snapshot_import", "blob") || snap_check(b, s->sig, "lm_snapshot_import", "snapshot")) return 1;
+  if (h.flags != s->flags) return fail("lm_snapshot_import: blob and snapshot differ in flag bit 0 (the collider cache)");
+  if (h.bytes != s->bytes) return fail("lm_snapshot_import: the blob's payload is not of this snapshot's size");
+  if (n < (long long)sizeof(h) + h.bytes) return fail("lm_snapshot_import: the blob is cut short");
+  HIPCHK(hipSetDevice(b->m->device));
+  hipStream_t used;
+  if (snap_enter(b, nullptr, &used)) return 1;
+  HIPCHK(hipMemcpyAsync(s->data, static_cast<const unsigned char*>(host) + sizeof(h), (size_t)s->bytes, hipMemcpyHostToDevice, used));
+  HIPCHK(hipStreamSynchronize(used));
+  s->step_index = h.step_index; s->saved = true;
+  return 0;
+}
 
 int lm_sync(lm_batch* b) {
   HIPCHK(hipSetDevice(b->m->device));

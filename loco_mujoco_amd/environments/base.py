@@ -39,6 +39,16 @@ class _HostState:
         self.site_xmat = {}
 
 
+class _EnvState:
+    """What :meth:`LocoEnv.save_state` returns: the device snapshot and the host fields ``step()`` reads."""
+
+    def __init__(self, env, snapshot, obs, restarted):
+        self.env, self.snapshot, self.obs, self.restarted = env, snapshot, obs, restarted
+
+    def close(self):
+        self.snapshot.close()
+
+
 class LocoEnv:
     """Base class of all locomotion environments (reference ``base.py:25``)."""
 
@@ -753,6 +763,56 @@ class LocoEnv:
                 self._term32, self._term64 = {}, None
         self._obs = obs[-1].copy()
         return obs, reward, (done & 1) != 0, info
+
+    # ------------------------------------------------------------------ save / load
+    def _save_state_refusal(self):
+        """Why :meth:`save_state` / :meth:`load_state` cannot serve this environment (a reason), or None."""
+        if self._blocks or self._grouped or self._n_models > 1:
+            return ("several models in one environment (block / grouped batches, a model drawn per episode) keep one device batch per "
+                    "model and host-side bookkeeping between them: a snapshot of one batch is not the environment's state")
+        if self._reward_device_spec() is None:
+            return ("the reward runs on the host (custom functor / foot-force columns) and may carry state of its own, which a device "
+                    "snapshot does not hold")
+        return None
+
+    def save_state(self):
+        """The environment's state after ``reset()`` — the device batch's snapshot (``HipBatch.snapshot``: everything a later control
+        step reads) and the host fields ``step()`` reads — as an opaque object for :meth:`load_state`. After ``load_state(s)`` the
+        environment continues bit for bit as it did after ``save_state()``: planners try action sequences with ``step_chunk`` and come
+        back. Random numbers of ``numpy.random`` (``reset()``) are not part of it. ``s.close()`` frees the device storage."""
+        if self._obs is None:
+            raise RuntimeError("call reset() before save_state()")
+        why = self._save_state_refusal()
+        if why is not None:
+            raise NotImplementedError("save_state: " + why)
+        if self._pending_state:
+            self._upload_state()            # what the next step() would do first: the snapshot then holds the episode's start
+        b = self.backend
+        restarted = getattr(b, "last_restarted", None)
+        return _EnvState(self, b.snapshot(), self._obs.copy(), None if restarted is None else restarted.copy())
+
+    def load_state(self, state):
+        """Back to what :meth:`save_state` returned (of THIS environment)."""
+        if not isinstance(state, _EnvState) or state.env is not self:
+            raise ValueError("load_state: not a state of this environment (save_state())")
+        why = self._save_state_refusal()
+        if why is not None:
+            raise NotImplementedError("load_state: " + why)
+        b = self.backend
+        b.restore(state.snapshot)
+        self._obs = state.obs.copy()
+        if state.restarted is None:
+            if hasattr(b, "last_restarted"):
+                del b.last_restarted
+        else:
+            b.last_restarted = state.restarted.copy()
+        # a reset() since the save is undone with the rest: nothing waits to be uploaded
+        self._pending_state = False
+        self._pending_dof_params = None
+        self._pending_variants = None
+        self._pending_compile = False
+        # step()'s host copies of the terminal-observation buffer (an output, not part of the snapshot) are fetched again
+        self._term32, self._term64 = {}, None
 
     def _tape_through_host(self, a):
         """``HipBatch.rollout_tape`` for the host array ``a`` [K, n_envs, nu]: one copy up (float32), the tapes back as numpy arrays
