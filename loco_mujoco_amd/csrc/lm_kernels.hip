@@ -4,6 +4,7 @@
 #include "lm_step.h"
 #include "lm_compile.h"
 #include "lm_snapshot.h"
+#include "lm_model_parse.h"
 #include <memory>
 
 using lmk::KArgs; using lmk::Task; using lmk::DevStats; using lmk::LaunchCtx;
@@ -22,23 +23,15 @@ int fail(const std::string& m) { g_err = m; return 1; }
 // ================================================================================================================
 struct lm_model {
   int device;
-  float* d_cm;
-  float* d_gt;               // geom table: full records of the geoms with a collider
-  float* d_mt;               // muscle table (models with muscles)
-  float* d_gpt;              // geom-pair table of the self-collision path
-  int n_gpt_floats;          // its size (0: the model has no self-collision pairs)
-  float* d_meshv;            // hull vertices of the mesh colliders
-  float* d_meshn;            // their neighbour lists (hull vertex graph)
-  float* d_bpt;              // body-pair table of the self-collision mid phase
-  float* d_meshadj;          // adjacency blocks of the hull vertices (convex-pair collider)
+  // the tables of lm_model_parse.h ParsedModel on the device: constant, geom, muscle (models with muscles), geom-pair, hull vertices, their
+  // neighbour lists, body pairs, adjacency blocks of the hull vertices; n_gpt_floats: size of the geom-pair table (0: no self-collision pairs)
+  float *d_cm, *d_gt, *d_mt, *d_gpt, *d_meshv, *d_meshn, *d_bpt, *d_meshadj; int n_gpt_floats;
   std::vector<float> nominal;  // [3][nv] damping | stiffness | frictionloss of the model
   lm::Params P; Task T;
-  int nroot;
-  std::vector<int> root_dofs;
+  int family;                // the kernel family that serves the model (lm_families.h pick_family; -1: none is compiled for it)
   bool root_limited;         // a root dof with an active-able limit (lm_batch_set_replay)
   size_t lds_limit;          // LDS of one CU in bytes: what the runtime reports, or kLdsAssumed where it reports the 64 KB default only
   bool lds_reported;         // true: lds_limit is the runtime's figure
-  bool root_xyz;             // the root's first three dofs are slides along +x, +y, +z in a root frame that is the world's (lm_core.h ROOT_XYZ)
 };
 
 struct lm_batch {
@@ -85,10 +78,6 @@ struct lm_batch {
   // owns (null with a caller's buffer), and the fourth array of every pinned result set, [N][nobs] float64 (lm_pinned_terminal_obs)
   float *term_obs, *term_own; double* h_term64[LM_PINNED_SLOTS];
 };
-// which kernel family serves a model (lm_family.hip): the quadruped family gets a specialised step kernel
-// <3 links, 6 slots, Euler, elliptic, self-collisions>; the humanoid families (five- and six-link chains) are compiled for
-// condim-3 pyramids only (T.all_pyr3, checked when the model is created): the elliptic code compiles out and the contact
-// slots are compact. Everything else: generic kernels, cone read at run time, plain layout only.
 // A/B switches of the probe builds (tools/probes: `make EXTRA=-DLM_PROBES ...`). The shipped library reads NO environment variable:
 // tests/test_abi_exports.py checks that `getenv` is not among its undefined symbols.
 #ifdef LM_PROBES
@@ -97,53 +86,28 @@ struct lm_batch {
 #define LM_PROBE_ENV(name) ((const char*)nullptr)
 #endif
 
-static int family_of(const lm_batch* b) {
-  const Task& T = b->m->T;
-  const bool big = T.max_links > 3, six = T.max_links > 5, rk4 = b->m->P.integrator == LM_INT_RK4, few = T.max_contacts <= 4;
-  static const bool generic = LM_PROBE_ENV("LM_GENERIC_KERNELS") != nullptr;      // A/B: run-time cone for the humanoids
-  const bool pyr3 = T.all_pyr3 && !generic;
-  // seven-link chains (the mesh-foot humanoid): RK4, condim-3 pyramids, no muscles, the pair pass and the joint equality rows
-  if (T.max_links > 6) return (rk4 && T.na == 0 && pyr3) ? 11 : -1;
-  if (six) return (!rk4 && T.na == 0 && pyr3) ? 7 : -1;      // (with or without self-collision tables: its regular kernels detect, its replay kernel collides)
-  // five-link humanoids whose lowering carries self-collision tables (bone hulls, link meshes, cylinders): the pair families
-  if (big && T.npair > 0 && pyr3) return rk4 ? (T.na == 0 ? 8 : 6) : (T.na == 0 ? 9 : 10);
-  // (the quadruped family's Hessian takes the root's translation columns as unit rows: lm_core.h ROOT_XYZ; another root -> generic kernels)
-  if (!big && !rk4 && T.na == 0 && b->m->P.cone == LM_CONE_ELLIPTIC && b->m->root_xyz) return 0;
-  // (families 1 / 3 — four contact slots per chain — are gone: since round 4 every five-link humanoid without muscles runs in the
-  // eight-slot families, where a fifth contact on a leg does not abandon the control step)
-  if (big && rk4 && T.na == 0 && pyr3) return 2;
-  if (big && !rk4 && T.na == 0 && pyr3) return 4;
-  if (big && !rk4 && T.na > 0 && few && pyr3) return 5;
-  return 6;
-}
-
-static bool family_has_replicas(const lm_batch* b) { return family_of(b) != 6; }
-static bool family_has_pairs(int fam) { return fam == 0 || fam == 7 || fam == 8 || fam == 9 || fam == 10 || fam == 11; }
-static bool family_has_equality_rows(int fam) { return fam == 11; }
+static lmk::Family traits(const lm_batch* b) { return lmk::family(b->m->family); }      // (lm_families.h; of a model without a family: all false)
+static bool one_layout_only(const lm_batch* b) { return b->m->family >= 0 && !traits(b).specialised(); }
 
 constexpr size_t kLdsAssumed = 160 * 1024;      // LDS of a gfx950 CU (lm_core.h: LaneMem)
 
-static const lmk::family_fn kFamilyTable[lmk::LMK_NFAMILY][3] = {
-      {lmk::launch_f0p0, lmk::launch_f0p1, lmk::launch_f0p2}, {nullptr, nullptr, nullptr},
-      {lmk::launch_f2p0, lmk::launch_f2p1, lmk::launch_f2p2}, {nullptr, nullptr, nullptr},
-      {lmk::launch_f4p0, lmk::launch_f4p1, lmk::launch_f4p2}, {lmk::launch_f5p0, lmk::launch_f5p1, lmk::launch_f5p2},
-      {lmk::launch_f6p0, lmk::launch_f6p1, lmk::launch_f6p2}, {lmk::launch_f7p0, lmk::launch_f7p1, lmk::launch_f7p2},
-      {lmk::launch_f8p0, lmk::launch_f8p1, lmk::launch_f8p2}, {lmk::launch_f9p0, lmk::launch_f9p1, lmk::launch_f9p2},
-      {lmk::launch_f10p0, lmk::launch_f10p1, lmk::launch_f10p2}, {lmk::launch_f11p0, lmk::launch_f11p1, lmk::launch_f11p2}};
+// the launch functions of the lm_family.hip objects, [family][part]: from the one list of families (absent ids: null)
+static lmk::family_fn kFamilyTable[lmk::LMK_NFAMILY][3];
+#define LM_X(id, ...) kFamilyTable[id][0] = lmk::launch_f##id##p0; kFamilyTable[id][1] = lmk::launch_f##id##p1; kFamilyTable[id][2] = lmk::launch_f##id##p2;
+static const bool kFamilyTableFilled = [] { LM_FAMILY_LIST(LM_X) return true; }();
+#undef LM_X
 
 // The LDS a launch of `kind` (lm_step.h LMK_*) of family `fam` takes at `epb` environments per workgroup for a model whose constant table
 // uses `cm_used` floats: asked of the launch code itself (LaunchCtx::probe — nothing is launched, no device is touched). false: the
 // family has no kernel of that kind.
 static bool lds_of(int fam, int kind, int epb, int cm_used, int max_links, lmk::LdsUse* out) {
-  if (fam < 0 || fam >= lmk::LMK_NFAMILY || !kFamilyTable[fam][0] || epb < 1) return false;
-  KArgs a;
-  memset(&a, 0, sizeof(a));
+  if (!lmk::family(fam).present || kind < 0 || kind >= lmk::LMK_NKINDS || epb < 1) return false;      // (whether it has the kind: the object answers)
+  KArgs a; memset(&a, 0, sizeof(a));
   a.T.cm_used = cm_used; a.T.max_links = max_links; a.epb = epb; a.N = epb;
-  lmk::LdsUse u = {0, 0};
-  const LaunchCtx L = {nullptr, epb, epb, 0, nullptr, &u, 0};
-  for (int p = 0; p < 3; p++)
-    if (kFamilyTable[fam][p](L, a, kind) && u.stat + u.dyn > 0) { *out = u; return true; }
-  return false;
+  lmk::LdsUse u = {0, 0}; const LaunchCtx L = {nullptr, epb, epb, 0, nullptr, &u, 0};
+  const bool has = kFamilyTable[fam][lmk::kKinds[kind].part](L, a, kind);
+  if (has) *out = u;
+  return has;
 }
 
 // Why the batch cannot step at `epb` environments per workgroup: the first kernel of that layout — regular, per-environment parameters,
@@ -151,21 +115,16 @@ static bool lds_of(int fam, int kind, int epb, int cm_used, int max_links, lmk::
 // question for lm_forward_debug's kernel alone (run-time cone, full slot records: at 16 per workgroup it does not fit for most humanoid
 // models whose step kernels do, so lm_forward_debug is refused at its own call and not with the layout).
 static std::string layout_refusal(const lm_batch* b, int epb, bool fwd) {
-  const int fam = family_of(b);
+  const int fam = b->m->family;
   if (fam < 0) return "";
-  const bool plain = epb > 4;
-  static const char* names[lmk::LMK_NKINDS] = {"forward", "replicated", "plain", "replicated, joint parameters", "plain, joint parameters", "fused", "fused, joint parameters",
-                                               "replicated, model variants", "plain, model variants", "fused, model variants", "replay", "replay, joint parameters", "replay, model variants"};
   for (int kind = 0; kind < lmk::LMK_NKINDS; kind++) {
-    const bool rep4 = kind == lmk::LMK_REP4 || kind == lmk::LMK_DR_REP4 || kind == lmk::LMK_DRV_REP4 || kind == lmk::LMK_FUSED || kind == lmk::LMK_FUSED_DR || kind == lmk::LMK_FUSED_DRV;
-    const bool rep1 = kind == lmk::LMK_REP1 || kind == lmk::LMK_DR_REP1 || kind == lmk::LMK_DRV_REP1;
-    if ((kind == lmk::LMK_FWD) != fwd || (plain && rep4) || (!plain && rep1 && fam != 6)) continue;
+    if ((kind == lmk::LMK_FWD) != fwd || !lmk::kind_runs_at(traits(b), kind, epb)) continue;
     lmk::LdsUse u;
     if (!lds_of(fam, kind, epb, b->m->T.cm_used, b->m->T.max_links, &u)) continue;
     if (u.stat + u.dyn > b->m->lds_limit) {
       char why[400];
       snprintf(why, sizeof(why), "%d environments per workgroup: the %s kernel of family %d needs %zu B of LDS per workgroup (%zu B static + %zu B dynamic, "
-               "%d B of it this model's constant table), a compute unit has %zu B (%s)", epb, names[kind], fam, u.stat + u.dyn, u.stat, u.dyn,
+               "%d B of it this model's constant table), a compute unit has %zu B (%s)", epb, lmk::kKinds[kind].name, fam, u.stat + u.dyn, u.stat, u.dyn,
                (int)sizeof(float) * b->m->T.cm_used, b->m->lds_limit, b->m->lds_reported ? "reported by the runtime" : "assumed: the runtime reports the 64 KB default only");
       return why;
     }
@@ -182,8 +141,7 @@ static std::string layout_refusal(const lm_batch* b, int epb, bool fwd) {
 template <bool FWD>
 static void launch_variant(lm_batch* b, const KArgs& a) {
   static const bool no_replicas = LM_PROBE_ENV("LM_NO_REPLICAS") != nullptr;                  // A/B switch
-  const auto& table = kFamilyTable;
-  const int fam = family_of(b);
+  const int fam = b->m->family;
   if (fam < 0) { g_launch_err = "chains of six links are compiled for Euler, of seven links for RK4 — condim-3 pyramids, no muscles only"; return; }
   const LaunchCtx L = {b->stream, b->n_active, b->epb, b->m->lds_limit, &g_launch_err, nullptr, 0};
   if (b->n_active <= 0) return;            // an empty active list: nothing to run
@@ -192,22 +150,15 @@ static void launch_variant(lm_batch* b, const KArgs& a) {
     if (!g_layout_err.empty()) { g_launch_err = g_layout_err.c_str(); return; }
     b->lds_ok[FWD] = b->epb;
   }
-  if (fam == 6) {
+  if (!traits(b).specialised()) {
     if (b->m->T.na > 0) { g_launch_err = "muscle models need the <5 links, <=4 contacts per chain, Euler> family"; return; }
     if (b->dofprm) { g_launch_err = "per-environment joint parameters are not compiled for this model family"; return; }
-    table[6][b->m->P.integrator == LM_INT_RK4 ? 1 : 0](L, a, FWD ? lmk::LMK_FWD : lmk::LMK_REP1);
+    kFamilyTable[fam][b->m->P.integrator == LM_INT_RK4 ? 1 : 0](L, a, FWD ? lmk::LMK_FWD : lmk::LMK_REP1);      // (its parts: Euler | RK4)
     return;
   }
-  // the layout: replicated (4 quads per environment, workgroups of <= 4 environments), per-environment joint
-  // parameters (domain randomisation), fused rollouts (replicated layout only), or plain
-  int kind;
-  const bool rep = b->epb <= 4 && !no_replicas;
-  if (FWD) kind = lmk::LMK_FWD;
-  else if (a.nfused > 1) kind = b->nvar > 0 ? lmk::LMK_FUSED_DRV : (b->dofprm ? lmk::LMK_FUSED_DR : lmk::LMK_FUSED);
-  else if (b->nvar > 0) kind = rep ? lmk::LMK_DRV_REP4 : lmk::LMK_DRV_REP1;
-  else if (b->dofprm) kind = rep ? lmk::LMK_DR_REP4 : lmk::LMK_DR_REP1;
-  else kind = rep ? lmk::LMK_REP4 : lmk::LMK_REP1;
-  const int big = b->nvar > 0 ? lmk::LMK_BIG_DRV : (b->dofprm ? lmk::LMK_BIG_DR : lmk::LMK_BIG);
+  const int kind = lmk::pick_kind(FWD, a.nfused > 1, b->nvar > 0, b->dofprm != nullptr, b->epb <= 4 && !no_replicas);
+  const int big = lmk::find_kind(b->nvar > 0 ? 2 : (b->dofprm ? 1 : 0), lmk::kReplay, true);
+  const lmk::family_fn launch = kFamilyTable[fam][lmk::kKinds[kind].part], launch_big = kFamilyTable[fam][lmk::kKinds[big].part];
   KArgs r = a;
   r.reg_grid = (b->n_active + b->epb - 1) / b->epb; r.epoch = b->epoch; r.host_hint = b->h_hint;
   const bool replay = !FWD && a.replay_list;
@@ -239,7 +190,7 @@ static void launch_variant(lm_batch* b, const KArgs& a) {
       // launches ahead of the device would start them long before their launch: they would wait out their time-out and leave
       if (b->epoch >= 2 && hipStreamWaitEvent(b->stream2, b->ev_done[b->epoch & 1], 0) != hipSuccess) { g_launch_err = "stream wait failed"; return; }
       const LaunchCtx L2 = {b->stream2, b->N, want, b->m->lds_limit, &g_launch_err, nullptr, 0};
-      if (!table[fam][0](L2, p, big) && !table[fam][1](L2, p, big) && !table[fam][2](L2, p, big)) { g_launch_err = "no replay kernel in the family"; return; }
+      if (!launch_big(L2, p, big)) { g_launch_err = "no replay kernel in the family"; return; }
       if (g_launch_err) return;              // (launch_one refused: nothing is in flight)
       if (hipEventRecord(b->ev_join, b->stream2) != hipSuccess) { g_launch_err = "stream join failed"; return; }
       pollers = true;
@@ -257,7 +208,7 @@ static void launch_variant(lm_batch* b, const KArgs& a) {
       (void)hipMemset(b->replay_ctl, 0, sizeof(int) * 4);
     }
   };
-  if (!table[fam][0](L, r, kind) && !table[fam][1](L, r, kind) && !table[fam][2](L, r, kind)) { bail("no kernel of this kind in the family"); return; }
+  if (!launch(L, r, kind)) { bail("no kernel of this kind in the family"); return; }
   if (g_launch_err) { bail(g_launch_err); return; }
   if (replay) {
     // the drain pass, behind the regular launch AND the pollers: whatever is still listed; resets the control words. An empty
@@ -265,7 +216,7 @@ static void launch_variant(lm_batch* b, const KArgs& a) {
     if (pollers && hipStreamWaitEvent(b->stream, b->ev_join, 0) != hipSuccess) { bail("stream join failed"); return; }
     r.drain = 1; r.stats_off = 0;
     const LaunchCtx L3 = {b->stream, b->N, lmk::kReplayGrid, b->m->lds_limit, &g_launch_err, nullptr, 0};
-    if (!table[fam][0](L3, r, big) && !table[fam][1](L3, r, big) && !table[fam][2](L3, r, big)) { bail("no replay kernel in the family"); return; }
+    if (!launch_big(L3, r, big)) { bail("no replay kernel in the family"); return; }
     if (g_launch_err) { bail(g_launch_err); return; }
     if (hipEventRecord(b->ev_done[b->epoch & 1], b->stream) != hipSuccess) { bail("event record failed"); return; }
     b->epoch++;
@@ -284,158 +235,37 @@ int lm_device_count(void) {
 
 void lm_model_destroy(lm_model* m);
 
+static int upload(const std::vector<float>& v, float** dev) {
+  HIPCHK(hipMalloc(dev, sizeof(float) * v.size()));
+  HIPCHK(hipMemcpy(*dev, v.data(), sizeof(float) * v.size(), hipMemcpyHostToDevice));
+  return 0;
+}
+
 int lm_model_create(const double* cmod, size_t n, int device, lm_model** out) {
-  if (!cmod || n < LM_HEADER_SIZE + LM_CM_SIZE + LM_GT_SIZE) return fail("chain model too short");
-  if ((unsigned)cmod[LM_H_MAGIC] != (unsigned)LM_LMC_MAGIC) return fail("bad chain-model magic");
-  if ((int)cmod[LM_H_CM_SIZE] != LM_CM_SIZE || (int)cmod[LM_H_GT_SIZE] != LM_GT_SIZE) return fail("chain-model table size mismatch (regenerate include/lm_layout.h)");
-  if ((int)cmod[LM_H_MAXLINKS] > LM_MAXC) return fail("chains longer than 7 links are not supported");
-  if ((int)cmod[LM_HEADER_SIZE + LM_R_NDOF] != 6) return fail("root body must have 6 dofs");
-  const int n_muscle = (int)cmod[LM_H_NMUSCLE];
-  if (n_muscle < 0 || n_muscle > LM_MT_MAXMUS) return fail("bad muscle count");
-  if (n_muscle > 0 && n < (size_t)(LM_HEADER_SIZE + LM_CM_SIZE + LM_GT_SIZE + LM_MT_SIZE)) return fail("chain model lacks the muscle table");
-  if (n_muscle > 0 && (int)cmod[LM_H_INTEGRATOR] != LM_INT_EULER) return fail("muscles need the Euler integrator");
+  lmp::ParsedModel pm; std::string why;
+  if (!lmp::parse_model(cmod, n, &pm, &why)) return fail(why);      // (every check of the blob: lm_model_parse.h)
   HIPCHK(hipSetDevice(device));
   std::unique_ptr<lm_model, void (*)(lm_model*)> guard(new lm_model(), lm_model_destroy);      // freed on every error path
-  lm_model* m = guard.get();
-  m->device = device;
-  {
-    // the LDS one workgroup may take. A runtime that reports no more than the 64 KB every launch gets without opting in says nothing
-    // about the CU: then the 160 KB of a CDNA4 CU that lm_core.h's LaneMem budgets with
-    int per_block = 0;
-    if (hipDeviceGetAttribute(&per_block, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess) per_block = 0;
-    m->lds_reported = per_block > 64 * 1024;
-    m->lds_limit = m->lds_reported ? (size_t)per_block : kLdsAssumed;
-  }
-  std::vector<float> cm(LM_CM_SIZE);
-  for (int i = 0; i < LM_CM_SIZE; i++) cm[i] = (float)cmod[LM_HEADER_SIZE + i];
-  if (LM_PROBE_ENV("LM_NO_PAIRS")) for (int c = 0; c < LM_NCHAIN; c++) cm[LM_CM_CHAINS + LM_C_NLPAIR * LM_NCHAIN + c] = 0.0f;      // A/B: self-collision broad phase off
-  // (limited root joints: limit rows in the muscle families, the run-time-cone kernels and every family's replay kernel; the other
-  // regular kernels hand a control step with a root dof beyond its range to the replay kernel — lm_core.h ROOT_LIM)
-  m->root_limited = false;
-  for (int i = 0; i < 6; i++) if (cm[LM_R_DOFS + i * LM_D_SIZE + LM_D_LIMITED] != 0.0f) m->root_limited = true;
-  m->root_xyz = cm[LM_R_NDOF] == 6.0f;
-  for (int i = 0; i < 9; i++) if (cm[LM_R_R0 + i] != ((i % 4 == 0) ? 1.0f : 0.0f)) m->root_xyz = false;
-  for (int i = 0; i < 3; i++) {
-    const float* d = cm.data() + LM_R_DOFS + i * LM_D_SIZE;
-    if (d[LM_D_TYPE] != 0.0f) m->root_xyz = false;                       // (0 = slide: mjcf.JNT_SLIDE)
-    for (int k = 0; k < 3; k++) if (d[LM_D_AX + k] != ((k == i) ? 1.0f : 0.0f)) m->root_xyz = false;
-  }
-  HIPCHK(hipMalloc(&m->d_cm, sizeof(float) * LM_CM_SIZE));
-  HIPCHK(hipMemcpy(m->d_cm, cm.data(), sizeof(float) * LM_CM_SIZE, hipMemcpyHostToDevice));
-  {
-    std::vector<float> gt(LM_GT_SIZE);
-    for (int i = 0; i < LM_GT_SIZE; i++) gt[i] = (float)cmod[LM_HEADER_SIZE + LM_CM_SIZE + i];
-    HIPCHK(hipMalloc(&m->d_gt, sizeof(float) * LM_GT_SIZE));
-    HIPCHK(hipMemcpy(m->d_gt, gt.data(), sizeof(float) * LM_GT_SIZE, hipMemcpyHostToDevice));
-  }
-  m->d_mt = nullptr;
-  if (n_muscle > 0) {
-    std::vector<float> mt(LM_MT_SIZE);
-    for (int i = 0; i < LM_MT_SIZE; i++) mt[i] = (float)cmod[LM_HEADER_SIZE + LM_CM_SIZE + LM_GT_SIZE + i];
-    for (int c = 0; c < LM_NCHAIN; c++) if ((int)mt[LM_NCHAIN + c] > LM_MAXMUS) { return fail("too many muscles on one chain"); }
-    HIPCHK(hipMalloc(&m->d_mt, sizeof(float) * LM_MT_SIZE));
-    HIPCHK(hipMemcpy(m->d_mt, mt.data(), sizeof(float) * LM_MT_SIZE, hipMemcpyHostToDevice));
-  }
-  Task& T = m->T;
-  T.na = n_muscle;
-  {
-    const int nv = (int)cmod[LM_H_NV];
-    m->nominal.assign((size_t)3 * nv, 0.0f);
-    auto put = [&](const float* blk, int stride) {
-      const int d = (int)blk[LM_D_DOF * stride];
-      if (d < 0 || d >= nv) return;
-      m->nominal[d] = blk[LM_D_DAMP * stride]; m->nominal[nv + d] = blk[LM_D_STIFF * stride]; m->nominal[2 * nv + d] = blk[LM_D_FLOSS * stride];
-    };
-    for (int i = 0; i < 6; i++) put(cm.data() + LM_R_DOFS + i * LM_D_SIZE, 1);
-    for (int c = 0; c < LM_NCHAIN; c++) {
-      const int nl = (int)cm[LM_CM_CHAINS + LM_C_NLINKS * LM_NCHAIN + c];
-      for (int k = 0; k < nl; k++) put(cm.data() + LM_CM_CHAINS + (LM_C_LINKS + k * LM_LINK_SIZE) * LM_NCHAIN + c, LM_NCHAIN);
-    }
-  }
-  T.nv = (int)cmod[LM_H_NV]; T.nu = (int)cmod[LM_H_NU]; T.nobs = (int)cmod[LM_H_NOBS]; T.ngoal = (int)cmod[LM_H_NGOAL];
-  T.nsub = (int)cmod[LM_H_NSUBSTEPS]; T.reward_type = (int)cmod[LM_H_REWARD_TYPE];
-  T.n_chains = (int)cmod[LM_H_NCHAINS]; T.max_links = (int)cmod[LM_H_MAXLINKS]; T.ngrf = (int)cmod[LM_H_NGRF];
-  T.max_contacts = (int)cmod[LM_H_MAXCONTACTS];
-  T.npair = (int)cmod[LM_H_NGPAIR];
-  {
-    // every geom with a device collider is a condim-3 contact under pyramidal cones?
-    T.all_pyr3 = (int)cmod[LM_H_CONE] == LM_CONE_PYRAMIDAL;
-    for (int c = 0; c < LM_NCHAIN && T.all_pyr3; c++) {
-      const int ng = (int)cmod[LM_HEADER_SIZE + LM_CM_CHAINS + LM_C_NGEOMS * LM_NCHAIN + c];
-      for (int g = 0; g < ng; g++) if ((int)cmod[LM_HEADER_SIZE + LM_CM_SIZE + (g * LM_G_SIZE + LM_G_DIM) * LM_NCHAIN + c] != 3) T.all_pyr3 = 0;
-    }
-  }
-  T.cm_used = ((int)cmod[LM_H_CM_USED] + 63) & ~63;          // keeps lane memory 256-byte aligned behind the table
-  if (T.cm_used <= 0 || T.cm_used > ((LM_CM_SIZE + 63) & ~63)) { return fail("bad constant-table extent"); }
-  if (T.ngoal > 4) { return fail("more than 4 goal entries"); }
-  for (int i = 0; i < 8; i++) T.rp[i] = (float)cmod[LM_H_REWARD_P0 + i];
+  lm_model* m = guard.get(); m->device = device;
+  // the LDS one workgroup may take. A runtime that reports no more than the 64 KB every launch gets without opting in says nothing
+  // about the CU: then the 160 KB of a CDNA4 CU that lm_core.h's LaneMem budgets with
+  int per_block = 0;
+  if (hipDeviceGetAttribute(&per_block, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess) per_block = 0;
+  m->lds_reported = per_block > 64 * 1024;
+  m->lds_limit = m->lds_reported ? (size_t)per_block : kLdsAssumed;
+  if (LM_PROBE_ENV("LM_NO_PAIRS")) for (int c = 0; c < LM_NCHAIN; c++) pm.cm[LM_CM_CHAINS + LM_C_NLPAIR * LM_NCHAIN + c] = 0.0f;      // A/B: self-collision broad phase off
+  m->T = pm.T; m->root_limited = pm.root_limited; m->n_gpt_floats = pm.n_gpt_floats; m->nominal = std::move(pm.nominal);
+  static const bool generic = LM_PROBE_ENV("LM_GENERIC_KERNELS") != nullptr;      // A/B: run-time cone for the humanoids
+  m->family = lmk::pick_family({pm.T.max_links, pm.T.max_contacts, pm.integrator, pm.cone, pm.T.na, pm.T.npair, pm.T.all_pyr3 != 0, pm.root_xyz}, generic);
+  if (upload(pm.cm, &m->d_cm) || upload(pm.gt, &m->d_gt) || (!pm.mt.empty() && upload(pm.mt, &m->d_mt)) || upload(pm.gpt, &m->d_gpt) ||
+      upload(pm.meshv, &m->d_meshv) || upload(pm.meshn, &m->d_meshn) || upload(pm.bpt, &m->d_bpt) || upload(pm.meshadj, &m->d_meshadj)) return 1;
   lm::Params& P = m->P;
-  P.h = (float)cmod[LM_H_TIMESTEP];
-  P.g = lm::V3{(float)cmod[LM_H_GX], (float)cmod[LM_H_GY], (float)cmod[LM_H_GZ]};
-  P.iterations = (int)cmod[LM_H_ITERATIONS];
+  P.h = pm.h; P.g = lm::V3{pm.g[0], pm.g[1], pm.g[2]}; P.iterations = pm.iterations; P.scale = pm.scale; P.nv = pm.T.nv;
   P.tolerance = 1e-6f;      // float32 stand-in for MuJoCo's 1e-8 (the gradient itself carries ~1e-6 relative noise)
-  P.nv = T.nv;
-  P.integrator = (int)cmod[LM_H_INTEGRATOR]; P.cone = (int)cmod[LM_H_CONE]; P.act_position = (int)cmod[LM_H_ACTMODE];
-  P.scale = 1.0f / ((float)cmod[LM_H_MEANINERTIA] * (float)T.nv);
-  P.off_runsup = (int)cmod[LM_H_OFF_RUNSUP];
-  P.gt = m->d_gt;
-  P.cmg = m->d_cm;
-  {
-    const size_t ngp = (size_t)cmod[LM_H_NGPAIR], off = (size_t)cmod[LM_H_OFF_GPT];
-    if (ngp > 0 && n < off + ngp * LM_GPAIR_SIZE) return fail("chain model lacks the geom-pair table");
-    std::vector<float> gpt(ngp * LM_GPAIR_SIZE + 1, 0.0f);
-    for (size_t i = 0; i < ngp * LM_GPAIR_SIZE; i++) gpt[i] = (float)cmod[off + i];
-    HIPCHK(hipMalloc(&m->d_gpt, sizeof(float) * gpt.size()));
-    HIPCHK(hipMemcpy(m->d_gpt, gpt.data(), sizeof(float) * gpt.size(), hipMemcpyHostToDevice));
-    P.gpt = m->d_gpt;
-    m->n_gpt_floats = (int)(ngp * LM_GPAIR_SIZE);
-  }
-  {
-    const size_t nmv = (size_t)cmod[LM_H_NMESHV], off = (size_t)cmod[LM_H_OFF_MESHV];
-    if (nmv > 0 && n < off + 4 * nmv) return fail("chain model lacks the mesh-vertex table");
-    std::vector<float> mv(4 * nmv + 4, 0.0f);
-    for (size_t i = 0; i < 4 * nmv; i++) mv[i] = (float)cmod[off + i];
-    HIPCHK(hipMalloc(&m->d_meshv, sizeof(float) * mv.size()));
-    HIPCHK(hipMemcpy(m->d_meshv, mv.data(), sizeof(float) * mv.size(), hipMemcpyHostToDevice));
-    P.meshv = m->d_meshv;
-  }
-  {
-    const size_t nmn = (size_t)cmod[LM_H_NMESHN], off = (size_t)cmod[LM_H_OFF_MESHN];
-    if (nmn > 0 && n < off + nmn) return fail("chain model lacks the hull-vertex neighbour table");
-    std::vector<float> mn(nmn + 1, -1.0f);
-    for (size_t i = 0; i < nmn; i++) mn[i] = (float)cmod[off + i];
-    HIPCHK(hipMalloc(&m->d_meshn, sizeof(float) * mn.size()));
-    HIPCHK(hipMemcpy(m->d_meshn, mn.data(), sizeof(float) * mn.size(), hipMemcpyHostToDevice));
-    P.meshn = m->d_meshn;
-  }
-  {
-    const size_t nbp = (size_t)cmod[LM_H_NBPAIR], off = (size_t)cmod[LM_H_OFF_BPT];
-    if (nbp > 0 && n < off + nbp * LM_BP_SIZE) return fail("chain model lacks the body-pair table");
-    std::vector<float> bp(nbp * LM_BP_SIZE + 1, 0.0f);
-    for (size_t i = 0; i < nbp * LM_BP_SIZE; i++) bp[i] = (float)cmod[off + i];
-    HIPCHK(hipMalloc(&m->d_bpt, sizeof(float) * bp.size()));
-    HIPCHK(hipMemcpy(m->d_bpt, bp.data(), sizeof(float) * bp.size(), hipMemcpyHostToDevice));
-    P.bpt = m->d_bpt;
-  }
-  {
-    const size_t na = (size_t)cmod[LM_H_NMESHADJ], off = (size_t)cmod[LM_H_OFF_MESHADJ];
-    if (na > 0 && n < off + 4 * na) return fail("chain model lacks the hull adjacency blocks");
-    std::vector<float> ma(4 * na + 64, 0.0f);                  // padded: a step of the hill climbing fetches eight entries at once
-    for (size_t i = 0; i < 4 * na; i++) ma[i] = (float)cmod[off + i];
-    HIPCHK(hipMalloc(&m->d_meshadj, sizeof(float) * ma.size()));
-    HIPCHK(hipMemcpy(m->d_meshadj, ma.data(), sizeof(float) * ma.size(), hipMemcpyHostToDevice));
-    P.meshadj = m->d_meshadj;
-  }
+  P.integrator = pm.integrator; P.cone = pm.cone; P.act_position = pm.act_position; P.off_runsup = pm.off_runsup; P.neq = pm.neq; P.off_eq = pm.off_eq;
+  P.gt = m->d_gt; P.cmg = m->d_cm; P.gpt = m->d_gpt; P.meshv = m->d_meshv; P.meshn = m->d_meshn; P.bpt = m->d_bpt; P.meshadj = m->d_meshadj;
   P.ls_tol = 1e-2f; P.ls_iters = 12; P.ls_noise = 2e-6f; P.ablate = 0;
-  P.root_limited = m->root_limited ? 1 : 0;
-  P.root_xyz = m->root_xyz ? 1 : 0;
-  P.neq = (int)cmod[LM_H_NEQ]; P.off_eq = (int)cmod[LM_H_OFF_EQ];
-  if (P.neq < 0 || (P.neq > 0 && (P.off_eq <= 0 || P.off_eq + P.neq * LM_EQ_SIZE > LM_CM_SIZE))) return fail("bad equality-record table");
-  for (int i = 0; i < P.neq; i++) {
-    const float* r = cm.data() + P.off_eq + i * LM_EQ_SIZE;
-    const int lane = (int)r[LM_EQ_LANE], link = (int)r[LM_EQ_LINK];
-    if (lane < 0 || lane >= LM_NCHAIN || link < 0 || link >= (int)cm[LM_CM_CHAINS + LM_C_NLINKS * LM_NCHAIN + lane]) return fail("equality record outside the chains");
-  }
+  P.root_limited = pm.root_limited ? 1 : 0; P.root_xyz = pm.root_xyz ? 1 : 0;
   P.ls_grid[0] = 0.25f; P.ls_grid[1] = 0.0625f; P.ls_grid[2] = 0.015625f;
   if (const char* v = LM_PROBE_ENV("LM_LS_GRID")) sscanf(v, "%f,%f,%f", &P.ls_grid[0], &P.ls_grid[1], &P.ls_grid[2]);   // A/B knob
   if (const char* v = LM_PROBE_ENV("LM_LS_NOISE")) P.ls_noise = (float)atof(v);
@@ -449,14 +279,7 @@ int lm_model_create(const double* cmod, size_t n, int device, lm_model** out) {
 
 void lm_model_destroy(lm_model* m) {
   if (!m) return;
-  if (m->d_cm) (void)hipFree(m->d_cm);
-  if (m->d_gt) (void)hipFree(m->d_gt);
-  if (m->d_gpt) (void)hipFree(m->d_gpt);
-  if (m->d_meshv) (void)hipFree(m->d_meshv);
-  if (m->d_meshn) (void)hipFree(m->d_meshn);
-  if (m->d_bpt) (void)hipFree(m->d_bpt);
-  if (m->d_meshadj) (void)hipFree(m->d_meshadj);
-  if (m->d_mt) (void)hipFree(m->d_mt);
+  for (float* p : {m->d_cm, m->d_gt, m->d_gpt, m->d_meshv, m->d_meshn, m->d_bpt, m->d_meshadj, m->d_mt}) if (p) (void)hipFree(p);
   delete m;
 }
 
@@ -530,13 +353,12 @@ int lm_batch_create(lm_model* m, int n_envs, lm_batch** out) {
   b->replay = 1;
   {
     // a model with self-collision tables needs a kernel family with the pair pass: anything else would silently not simulate them
-    const int fam = family_of(b);
-    if (m->T.npair > 0 && !family_has_pairs(fam)) {
+    if (m->T.npair > 0 && !traits(b).pairs()) {
       delete b;
       return fail("the model carries self-collision tables but its kernel family has no pair pass (RK4 with muscles, or a cone / condim the pair families are not compiled for)");
     }
     // the same for joint equality rows: compiled into the seven-link family only (lm_core.h EQ_ROWS)
-    if (m->P.neq > 0 && !family_has_equality_rows(fam)) {
+    if (m->P.neq > 0 && !traits(b).eq_rows()) {
       delete b;
       return fail("the model carries joint equality rows but its kernel family has none (they are compiled into the seven-link family only)");
     }
@@ -553,7 +375,7 @@ int lm_batch_set_replay(lm_batch* b, int enabled) {
   if (!b) return fail("null batch");
   // 2 (tests): every control step goes through the replay kernel; 3 / 4 = 1 / 2 without pollers: the replay kernel only as the pass
   // behind the regular launch (profilers that run one kernel at a time would leave the pollers waiting for their time-out)
-  if (!enabled && b->m->T.na == 0 && family_of(b) >= 0 && family_of(b) != 6) {
+  if (!enabled && b->m->T.na == 0 && traits(b).specialised()) {
     // the regular kernels of the families without muscles have no limit rows for the root dofs: without the replay kernel a root dof
     // beyond its range would run without its row (flagged per step, but wrong physics) — refuse rather than offer that
     if (b->m->root_limited) return fail("this model has a limited root joint whose limit rows live in the replay kernel: replay cannot be switched off");
@@ -571,7 +393,7 @@ int lm_batch_set_layout(lm_batch* b, int envs_per_workgroup) {
   const int def = b->N < 4 ? b->N : 4;
   if (envs_per_workgroup == 4) envs_per_workgroup = def;      // the advertised default, also for a batch of fewer than four environments
   if (envs_per_workgroup != def && envs_per_workgroup != 8 && envs_per_workgroup != 16) return fail("environments per workgroup: 4 (replicated layout), 8 or 16 (plain layout)");
-  if (envs_per_workgroup > def && !family_has_replicas(b)) return fail("the generic kernel family has one layout only");
+  if (envs_per_workgroup > def && one_layout_only(b)) return fail("the generic kernel family has one layout only");
   // a layout whose kernels ask for more LDS than a CU has is refused HERE, with the byte counts, before anything is launched (the
   // muscle humanoid with pair tables at 16: 169 048 B against 163 840 B — launched, that ended in an illegal memory access)
   { const std::string why = layout_refusal(b, envs_per_workgroup, false); if (!why.empty()) return fail(why); }
@@ -722,7 +544,7 @@ int lm_set_dof_params(lm_batch* b, const float* damping, const float* stiffness,
   if (!b->dofprm) {
     // fail HERE, not at the first launch: the generic kernels (and six-link RK4 models, which have no kernel at all) are not
     // compiled for per-environment joint parameters / model variants
-    if (family_of(b) < 0 || family_of(b) == 6)
+    if (!traits(b).env_params())
       return fail("per-environment joint parameters and model variants are not compiled for this model's kernel family (generic kernels)");
     std::vector<float> init((size_t)3 * nv * N);
     for (int p = 0; p < 3; p++) for (int d = 0; d < nv; d++) for (int e = 0; e < N; e++) init[((size_t)p * nv + d) * N + e] = b->m->nominal[(size_t)p * nv + d];
@@ -974,17 +796,16 @@ static KArgs make_args(lm_batch* b) {
   a.N = b->N; a.P = b->m->P; a.T = b->m->T; a.stats = b->stats;
   a.epb = b->epb; a.timers = b->timers; a.tline = b->tline; a.nfused = 1;
   // speculate / replay: every family but the generic one has a replay kernel
-  if (b->replay && family_of(b) >= 0 && family_of(b) != 6) { a.replay_list = b->replay_list; a.replay_ctl = b->replay_ctl; a.stall = b->stall; a.replay_mark = b->replay_mark;
+  if (b->replay && traits(b).specialised()) { a.replay_list = b->replay_list; a.replay_ctl = b->replay_ctl; a.stall = b->stall; a.replay_mark = b->replay_mark;
     static const bool no_resume = LM_PROBE_ENV("LM_NO_RESUME") != nullptr;       // A/B: restart abandoned control steps from their own state (round 4)
     if (!no_resume) { a.hq = b->hq; a.hv = b->hv; a.hw = b->hw; }
     a.hsub = b->hsub;
     static const bool no_premark = LM_PROBE_ENV("LM_NO_PREMARK") != nullptr;       // A/B: every control step starts in the regular kernel (round 4)
     if (!no_premark) {
       a.premark = b->premark;
-      // the regular kernels' capacity per chain (lm_family.hip / lm_core.h LaneMem: contact slots, queued convex pairs, pair results)
+      // the regular kernels' capacity per chain (lm_families.h / lm_core.h LaneMem: contact slots, queued convex pairs, pair results)
       const Task& T = b->m->T;
-      const int fam = family_of(b);
-      a.reg_ns = fam == 0 ? 6 : (fam == 5 ? 4 : 8); a.reg_q = T.max_links >= 5 ? 24 : 8; a.reg_r = a.reg_ns < 8 ? a.reg_ns : 8;
+      a.reg_ns = traits(b).NS; a.reg_q = T.max_links >= 5 ? 24 : 8; a.reg_r = a.reg_ns < 8 ? a.reg_ns : 8;
     } a.replay_all = b->replay == 2 || b->replay == 4; }
   static const bool no_xcd_map = LM_PROBE_ENV("LM_NO_XCD_MAP") != nullptr;
   a.xcd_map = no_xcd_map ? 0 : 1;
@@ -1026,7 +847,7 @@ int lm_batch_set_active(lm_batch* b, const int32_t* env_ids, int count) {
   HIPCHK(hipSetDevice(b->m->device));
   HIPCHK(hipStreamSynchronize(b->stream));
   if (!env_ids) { b->n_active = b->N; if (b->env_map) { HIPCHK(hipFree(b->env_map)); b->env_map = nullptr; } return 0; }
-  if (family_of(b) == 0) return fail("active lists are not compiled into the quadruped's kernels (lm_step.h: the indirection costs the bench kernel 0.9 %)");
+  if (traits(b).no_active_lists()) return fail("active lists are not compiled into the quadruped's kernels (lm_step.h: the indirection costs the bench kernel 0.9 %)");
   if (count < 0 || count > b->N) return fail("active list: more entries than environments");
   std::vector<char> seen((size_t)b->N, 0);
   for (int i = 0; i < count; i++) {
@@ -1263,7 +1084,7 @@ int lm_rollout_fused(lm_batch* b, int n_steps, int steps_per_launch, int action_
   if (action_mode != 0 && action_mode != 1) return fail("action_mode must be 0 (zero) or 1 (uniform random)");
   if (steps_per_launch < 1) return fail("steps_per_launch must be >= 1");
   static const bool no_replicas = LM_PROBE_ENV("LM_NO_REPLICAS") != nullptr;
-  if (b->epb > 4 || no_replicas || !family_has_replicas(b)) steps_per_launch = 1;     // no fused kernels for the full-wave layout
+  if (b->epb > 4 || no_replicas || one_layout_only(b)) steps_per_launch = 1;     // no fused kernels for the full-wave layout
   if (b->mc_ib) steps_per_launch = 1;       // a restart inside a launch needs its fresh model before the episode's first step
   KArgs a = make_args(b);
   a.action = nullptr; a.action_mode = action_mode == 0 ? 1 : 2;   // kernel: 1 = zero action, 2 = random
@@ -1300,7 +1121,7 @@ int lm_rollout_tape(lm_batch* b, int n_steps, int steps_per_launch, const float*
   if (d_term && !b->term_obs) return fail("lm_rollout_tape: d_term needs terminal observations enabled (lm_set_terminal_obs)");
   static const bool no_replicas = LM_PROBE_ENV("LM_NO_REPLICAS") != nullptr;
   // as in lm_rollout_fused: one control step per launch where there is no fused kernel (the launch's pointers then carry the offsets)
-  if (b->epb > 4 || no_replicas || !family_has_replicas(b)) steps_per_launch = 1;
+  if (b->epb > 4 || no_replicas || one_layout_only(b)) steps_per_launch = 1;
   if (b->mc_ib) steps_per_launch = 1;
   KArgs a = make_args(b);            // the batch's own seed: a tape launch restarts episodes exactly like lm_step*
   a.action_mode = 0;

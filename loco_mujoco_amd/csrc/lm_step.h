@@ -44,6 +44,7 @@ __device__ __forceinline__ int lm_opaque_zero() { int z = 0; asm volatile("" : "
 #define LM_POW01(x, p) __builtin_amdgcn_exp2f((p) * __builtin_amdgcn_logf(x))   // v_exp_f32(p * v_log_f32(x))
 #define LM_CLOCK() ((long long)__builtin_readcyclecounter())
 #include "lm_core.h"
+#include "lm_families.h"
 #include "../../include/locohip.h"
 
 namespace lmk {
@@ -118,11 +119,6 @@ struct QuadDppT {
   }
 };
 using QuadDpp = QuadDppT<1>;
-
-struct Task {
-  int nv, nu, nobs, ngoal, nsub, reward_type, n_chains, max_links, na, ngrf, cm_used, max_contacts, all_pyr3, npair;
-  float rp[8];
-};
 
 struct DevStats { float env_steps, episodes, reward_sum, nan_resets, solver_iters, overflow, unhandled, ls_evals, ls_capped, it_ge8, selfprox, selfcon, replayed, natown, pad_[2]; };
 constexpr int kNStats = 14;
@@ -815,12 +811,6 @@ struct LaunchCtx { hipStream_t stream; int N, epb; size_t lds_limit; const char*
 // static LDS of step_kernel<..., NM, ...>: `mt` and `blk_stats` (both float arrays: no padding between them or in front of the dynamic part)
 constexpr size_t static_lds_bytes(int nm) { return sizeof(float) * ((size_t)(nm > 0 ? LM_MT_SIZE : 1) + kNStats); }
 
-// kernel kinds of one family (picked by the host, lm_kernels.hip::launch_variant)
-enum { LMK_FWD = 0, LMK_REP4, LMK_REP1, LMK_DR_REP4, LMK_DR_REP1, LMK_FUSED, LMK_FUSED_DR, LMK_DRV_REP4, LMK_DRV_REP1, LMK_FUSED_DRV,
-       LMK_BIG, LMK_BIG_DR, LMK_BIG_DRV /* the replay kernels, one per part */, LMK_NKINDS };
-constexpr int LMK_NFAMILY = 12;     // 0 quadruped, 2 humanoid RK4 8 slots, 4 Euler 8 slots, 5 muscles, 6 generic, 7 six-link chains (Euler, 8 slots), (1 / 3: the four-slot humanoid families, dropped in round 5)
-                                    // 8 / 9 / 10 = five-link humanoids WITH self-collisions (8 slots): RK4 | Euler | Euler + muscles
-                                    // 11 = seven-link chains WITH self-collisions and joint equality rows (RK4, 8 slots): the mesh-foot humanoid
 // Replicas of the replay kernels' ONE environment per workgroup. 4 (shipped): the regular kernels' arithmetic exactly — a control step
 // comes out bitwise the same from either kernel. 16 (-DLM_REPLAY_REP=16): the whole wave for the environment, everything that is dealt
 // over replicas / lanes dealt four times wider. Measured in round 5 (profiles/r5_notes.md §3): a hard HumanoidTorque costs 10.4 ms with
@@ -866,21 +856,26 @@ static void launch_term(K kernel, KT kernel_term, dim3 grid, dim3 block, size_t 
   else launch_one(kernel, grid, block, lane_floats, L, a);
 }
 
-// one robot family = (links per chain MC, contact slots per chain NS, integrator, compiled-in cone, muscles per chain NM, pair
-// pass PM of the regular kernels: 0 none, 1 with the convex collider, 2 without — the replay kernel has it)
+// the regular kernel of kind K (lm_families.h kKinds: DR, layout, fused): both instantiations (TERM: the terminal-observation store), block size, lane memory
+template <int MC, int NS, bool RK4, int CONE, int NM, int PM, int K>
+static void launch_regular(const LaunchCtx& L, const KArgs& a) {
+  constexpr Kind kd = kKinds[K];
+  constexpr int REP = kd.layout == kRep4 ? 4 : 1;
+  using LMm = lm::LaneMemFor<MC, NS, NM, (PM == 1 || PM == 2), CONE>;       // (as the kernel's own alias: detection-only kernels carry no pair extension)
+  launch_term(step_kernel<MC, NS, RK4, false, CONE, NM, kd.DR, REP, kd.fused, PM>, step_kernel<MC, NS, RK4, false, CONE, NM, kd.DR, REP, kd.fused, PM, true>,
+              dim3((L.N + L.epb - 1) / L.epb), dim3(4 * REP * L.epb), (size_t)LMm::kGroup * (REP == 4 ? 1 : (4 * L.epb + 15) / 16), L, a);
+}
+// one robot family: a row of lm_families.h (MC, NS, integrator, compiled-in cone, NM, pair pass PM of the regular kernels — the replay kernel has it)
 template <int MC, int NS, bool RK4, int CONE, int NM, int PART, int PM = 0>
 static bool launch_family(const LaunchCtx& L0, const KArgs& a, int kind) {
   LaunchCtx L = L0;
   L.stat_bytes = static_lds_bytes(NM);
-  const dim3 grid((L.N + L.epb - 1) / L.epb);
-  using LMm = lm::LaneMemFor<MC, NS, NM, (PM == 1 || PM == 2), CONE>;       // (as the kernel's own alias: detection-only kernels carry no pair extension)
-  const size_t plain = (size_t)LMm::kGroup * ((4 * L.epb + 15) / 16), rep = (size_t)LMm::kGroup;
+  if (kind < 0 || kind >= LMK_NKINDS || kKinds[kind].part != PART) return false;
   // the replay kernel: 128 contact slots per chain (one environment per workgroup: its whole LDS), the convex collider,
   // fused (it finishes the launch's control steps of its environments)
   constexpr int NSB = 128, PMB = (PM != 0) ? 1 : 0;
-  using LMb = lm::LaneMemFor<MC, NSB, NM, (PM != 0), CONE>;
-  if (kind == LMK_BIG || kind == LMK_BIG_DR || kind == LMK_BIG_DRV) {
-    if (kind != LMK_BIG + PART) return false;
+  if (kKinds[kind].layout == kReplay) {
+    using LMb = lm::LaneMemFor<MC, NSB, NM, (PM != 0), CONE>;
     KArgs b = a;
     b.epb = 1; b.xcd_map = 0;
     // L.epb carries the number of workgroups asked for here (pollers: a few; the drain pass: kReplayGrid). The statistics slots are
@@ -889,40 +884,21 @@ static bool launch_family(const LaunchCtx& L0, const KArgs& a, int kind) {
     launch_term(step_kernel<MC, NSB, RK4, false, CONE, NM, PART, kReplayRep, true, PMB>, step_kernel<MC, NSB, RK4, false, CONE, NM, PART, kReplayRep, true, PMB, true>, dim3(ngroups < want ? ngroups : want), dim3(4 * kReplayRep), (size_t)LMb::kPadded * 4, L, b);
     return true;
   }
-  if constexpr (PART == 0) {
-    // the forward-only (debug) kernel reads the cone at run time: full slot records (and always carries the convex collider)
-    if (kind == LMK_FWD) launch_one(step_kernel<MC, NS, RK4, true, -1, NM, 0, 1, false, PMB>, grid, dim3(4 * L.epb),
-                                    (size_t)lm::LaneMemFor<MC, NS, NM, (PM != 0), -1>::kGroup * ((4 * L.epb + 15) / 16), L, a);
-    else if (kind == LMK_REP4) launch_term(step_kernel<MC, NS, RK4, false, CONE, NM, 0, 4, false, PM>, step_kernel<MC, NS, RK4, false, CONE, NM, 0, 4, false, PM, true>, grid, dim3(16 * L.epb), rep, L, a);
-    else if (kind == LMK_REP1) launch_term(step_kernel<MC, NS, RK4, false, CONE, NM, 0, 1, false, PM>, step_kernel<MC, NS, RK4, false, CONE, NM, 0, 1, false, PM, true>, grid, dim3(4 * L.epb), plain, L, a);
-    else return false;
-  } else if constexpr (PART == 1) {
-    if (kind == LMK_DR_REP4) launch_term(step_kernel<MC, NS, RK4, false, CONE, NM, 1, 4, false, PM>, step_kernel<MC, NS, RK4, false, CONE, NM, 1, 4, false, PM, true>, grid, dim3(16 * L.epb), rep, L, a);
-    else if (kind == LMK_DR_REP1) launch_term(step_kernel<MC, NS, RK4, false, CONE, NM, 1, 1, false, PM>, step_kernel<MC, NS, RK4, false, CONE, NM, 1, 1, false, PM, true>, grid, dim3(4 * L.epb), plain, L, a);
-    else if (kind == LMK_FUSED) launch_term(step_kernel<MC, NS, RK4, false, CONE, NM, 0, 4, true, PM>, step_kernel<MC, NS, RK4, false, CONE, NM, 0, 4, true, PM, true>, grid, dim3(16 * L.epb), rep, L, a);
-    else if (kind == LMK_FUSED_DR) launch_term(step_kernel<MC, NS, RK4, false, CONE, NM, 1, 4, true, PM>, step_kernel<MC, NS, RK4, false, CONE, NM, 1, 4, true, PM, true>, grid, dim3(16 * L.epb), rep, L, a);
-    else return false;
-  } else {
-    // per-environment joint parameters AND model variants (lm_set_model_variants)
-    if (kind == LMK_DRV_REP4) launch_term(step_kernel<MC, NS, RK4, false, CONE, NM, 2, 4, false, PM>, step_kernel<MC, NS, RK4, false, CONE, NM, 2, 4, false, PM, true>, grid, dim3(16 * L.epb), rep, L, a);
-    else if (kind == LMK_DRV_REP1) launch_term(step_kernel<MC, NS, RK4, false, CONE, NM, 2, 1, false, PM>, step_kernel<MC, NS, RK4, false, CONE, NM, 2, 1, false, PM, true>, grid, dim3(4 * L.epb), plain, L, a);
-    else if (kind == LMK_FUSED_DRV) launch_term(step_kernel<MC, NS, RK4, false, CONE, NM, 2, 4, true, PM>, step_kernel<MC, NS, RK4, false, CONE, NM, 2, 4, true, PM, true>, grid, dim3(16 * L.epb), rep, L, a);
-    else return false;
-  }
-  return true;
+  // the forward-only (debug) kernel reads the cone at run time: full slot records (and always carries the convex collider)
+  if constexpr (PART == 0) if (kind == LMK_FWD) { launch_one(step_kernel<MC, NS, RK4, true, -1, NM, 0, 1, false, PMB>, dim3((L.N + L.epb - 1) / L.epb), dim3(4 * L.epb),
+                                                             (size_t)lm::LaneMemFor<MC, NS, NM, (PM != 0), -1>::kGroup * ((4 * L.epb + 15) / 16), L, a); return true; }
+  // the regular kinds that kKinds puts into this part (part 2: per-environment joint parameters AND model variants, lm_set_model_variants)
+#define LM_REGULAR(K) if constexpr (kKinds[K].part == PART) if (kind == K) { launch_regular<MC, NS, RK4, CONE, NM, PM, K>(L, a); return true; }
+  LM_REGULAR(LMK_REP4) LM_REGULAR(LMK_REP1) LM_REGULAR(LMK_DR_REP4) LM_REGULAR(LMK_DR_REP1) LM_REGULAR(LMK_FUSED) LM_REGULAR(LMK_FUSED_DR)
+  LM_REGULAR(LMK_DRV_REP4) LM_REGULAR(LMK_DRV_REP1) LM_REGULAR(LMK_FUSED_DRV)
+#undef LM_REGULAR
+  return false;
 }
 
-// defined in the lm_family.hip objects; false = this family/part has no kernel of that kind
+// defined in the lm_family.hip objects, three parts per family of lm_families.h; false = this family/part has no kernel of that kind
 typedef bool (*family_fn)(const LaunchCtx&, const KArgs&, int kind);
-bool launch_f0p0(const LaunchCtx&, const KArgs&, int); bool launch_f0p1(const LaunchCtx&, const KArgs&, int); bool launch_f0p2(const LaunchCtx&, const KArgs&, int);
-bool launch_f2p0(const LaunchCtx&, const KArgs&, int); bool launch_f2p1(const LaunchCtx&, const KArgs&, int); bool launch_f2p2(const LaunchCtx&, const KArgs&, int);
-bool launch_f4p0(const LaunchCtx&, const KArgs&, int); bool launch_f4p1(const LaunchCtx&, const KArgs&, int); bool launch_f4p2(const LaunchCtx&, const KArgs&, int);
-bool launch_f5p0(const LaunchCtx&, const KArgs&, int); bool launch_f5p1(const LaunchCtx&, const KArgs&, int); bool launch_f5p2(const LaunchCtx&, const KArgs&, int);
-bool launch_f6p0(const LaunchCtx&, const KArgs&, int); bool launch_f6p1(const LaunchCtx&, const KArgs&, int); bool launch_f6p2(const LaunchCtx&, const KArgs&, int);
-bool launch_f7p0(const LaunchCtx&, const KArgs&, int); bool launch_f7p1(const LaunchCtx&, const KArgs&, int); bool launch_f7p2(const LaunchCtx&, const KArgs&, int);
-bool launch_f8p0(const LaunchCtx&, const KArgs&, int); bool launch_f8p1(const LaunchCtx&, const KArgs&, int); bool launch_f8p2(const LaunchCtx&, const KArgs&, int);
-bool launch_f9p0(const LaunchCtx&, const KArgs&, int); bool launch_f9p1(const LaunchCtx&, const KArgs&, int); bool launch_f9p2(const LaunchCtx&, const KArgs&, int);
-bool launch_f10p0(const LaunchCtx&, const KArgs&, int); bool launch_f10p1(const LaunchCtx&, const KArgs&, int); bool launch_f10p2(const LaunchCtx&, const KArgs&, int);
-bool launch_f11p0(const LaunchCtx&, const KArgs&, int); bool launch_f11p1(const LaunchCtx&, const KArgs&, int); bool launch_f11p2(const LaunchCtx&, const KArgs&, int);
+#define LM_X(id, ...) bool launch_f##id##p0(const LaunchCtx&, const KArgs&, int); bool launch_f##id##p1(const LaunchCtx&, const KArgs&, int); bool launch_f##id##p2(const LaunchCtx&, const KArgs&, int);
+LM_FAMILY_LIST(LM_X)
+#undef LM_X
 
 }  // namespace lmk
