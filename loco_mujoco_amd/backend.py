@@ -256,6 +256,18 @@ def check_restore_args(n, src=None, mask=None, snapshot=None, batch=None):
     return "host", np.ascontiguousarray(np.where(a, np.arange(n), -1), dtype=np.int32)
 
 
+def _dev_ptr(x):
+    """A device buffer as a C pointer: None, a raw address (int), or an object with ``data_ptr()`` such as a torch tensor."""
+    if x is None:
+        return None
+    return C.c_void_p(int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x))
+
+
+def _stream_ptr(stream):
+    """A raw hipStream_t (int) as a C pointer; None: the library's own stream."""
+    return None if stream is None else C.c_void_p(int(stream))
+
+
 class HipModel:
     def __init__(self, chain_model, device=0):
         self.device = int(device)
@@ -305,7 +317,7 @@ class Snapshot:
     def save(self, stream=None, sync=True):
         """Save the batch's present state into this snapshot's storage (one kernel launch)."""
         check_restore_args(self.batch.n, snapshot=self, batch=self.batch)
-        _check(self._lib.lm_snapshot_save(self.batch._h, self._h, None if stream is None else C.c_void_p(int(stream)), int(bool(sync))))
+        _check(self._lib.lm_snapshot_save(self.batch._h, self._h, _stream_ptr(stream), int(bool(sync))))
         return self
 
     def to_bytes(self):
@@ -343,6 +355,9 @@ class HipBatch:
         d = model.dims
         self.nq, self.nv, self.nu, self.nobs, self.ngoal = d.nq, d.nv, d.nu, d.nobs, d.ngoal
         self.na = d.na
+        self._term_on, self._term_out = False, None              # terminal observations: enabled; a caller's tensor, kept alive
+        self._pinned = self._pinned_term = None                  # views of the pinned ring (step_pinned)
+        self._compiler_on, self.n_variants, self.n_model_draws, self._table_sizes = False, 0, 0, None
 
     def close(self):
         for snap in list(getattr(self, "_snapshots", ())):      # the batch's snapshots die with it (their storage first)
@@ -393,12 +408,8 @@ class HipBatch:
         returns; bit 1 (``done & 2``) = the episode ended on the device in this step (restarted from the reset table — ``obs``
         is then the first observation of the new episode — or, without auto-reset, the step that reached the horizon).
         ``done.bool()`` mixes truncation and restarts into the terminal flag; mask the bits."""
-        def ptr(x):
-            if x is None:
-                return None
-            return C.c_void_p(int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x))
-        _check(self._lib.lm_step_device(self._h, ptr(action), ptr(obs), ptr(reward), ptr(done),
-                                        None if stream is None else C.c_void_p(int(stream)), int(bool(sync))))
+        _check(self._lib.lm_step_device(self._h, _dev_ptr(action), _dev_ptr(obs), _dev_ptr(reward), _dev_ptr(done),
+                                        _stream_ptr(stream), int(bool(sync))))
 
     def set_dof_params(self, damping=None, stiffness=None, frictionloss=None, mask=None):
         """Per-environment joint parameters [n, nv] (domain randomisation); None leaves a parameter as it is."""
@@ -567,15 +578,15 @@ class HipBatch:
         PINNED_SLOTS pinned result sets owned by the batch: what a call returned stays intact for the next PINNED_SLOTS - 1 calls.
         With terminal observations enabled a fourth view follows: float64 [n, nobs] in the order of set_obs_order, whose rows with
         ``last_restarted`` set hold this step's terminal observation (the other rows: whatever the slot held)."""
-        if getattr(self, "_pinned", None) is None:
+        if self._pinned is None:
             self._pinned = self._pinned_views()
             self._slot = -1
         self._slot = (self._slot + 1) % self.PINNED_SLOTS
         _check(self._lib.lm_step_pinned(self._h, action64.ctypes.data_as(C.POINTER(C.c_double)), self._slot))
         obs, rew, done = self._pinned[self._slot]
         self.last_restarted = (done & 2) != 0
-        if getattr(self, "_term_on", False):
-            if getattr(self, "_pinned_term", None) is None:
+        if self._term_on:
+            if self._pinned_term is None:
                 self._pinned_term = self._pinned_term_views()
             return obs, rew, (done & 1) != 0, self._pinned_term[self._slot]
         return obs, rew, (done & 1) != 0
@@ -648,23 +659,18 @@ class HipBatch:
         (needs :meth:`enable_terminal_obs`; row [t, e] is written where ``done[t, e] & 2``, the others are left as they were).
         Bitwise what T calls of ``step_device`` produce. Returns the statistics (``sync=True``) or None."""
         T, stride, spl = check_tape_args(self.n, self.nu, self.nobs, actions, obs, reward, done, terminal, steps_per_launch, repeat, n_steps,
-                                         terminal_enabled=getattr(self, "_term_on", False))
-
-        def ptr(x):
-            if x is None:
-                return None
-            return C.c_void_p(int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x))
+                                         terminal_enabled=self._term_on)
         st = Stats()
-        _check(self._lib.lm_rollout_tape(self._h, T, spl, ptr(actions), stride, ptr(obs), ptr(reward), ptr(done), ptr(terminal),
-                                         None if stream is None else C.c_void_p(int(stream)), int(bool(sync)), C.byref(st) if sync else None))
+        _check(self._lib.lm_rollout_tape(self._h, T, spl, _dev_ptr(actions), stride, _dev_ptr(obs), _dev_ptr(reward), _dev_ptr(done), _dev_ptr(terminal),
+                                         _stream_ptr(stream), int(bool(sync)), C.byref(st) if sync else None))
         return st.as_dict() if sync else None
 
     # ---- snapshots (include/locohip.h lm_snapshot_*)
     def snapshot_signature(self):
         """What a snapshot must agree on with the batch, as far as this layer knows it (the library compares its own, fuller list —
         the joint-parameter arrays and the collider cache among it — and refuses with the field's name)."""
-        compiler = getattr(self, "n_model_draws", 0) if getattr(self, "_compiler_on", False) else 0
-        return (self.n, self.nv, self.na, self.nobs, int(getattr(self, "n_variants", 0)), int(compiler))
+        compiler = self.n_model_draws if self._compiler_on else 0
+        return (self.n, self.nv, self.na, self.nobs, int(self.n_variants), int(compiler))
 
     def snapshot(self, keep_collider_cache=True, stream=None, sync=True):
         """Save the state of every environment on the device and return the :class:`Snapshot`: everything a later control step reads,
@@ -692,7 +698,7 @@ class HipBatch:
                     torch.cuda.current_stream(val.device).synchronize()                          # made on torch's stream, read on another
             self._src_keep = val          # alive until the next restore: with sync=False the copy may still be queued
             ptr = C.c_void_p(int(val.data_ptr()))
-        _check(self._lib.lm_snapshot_restore(self._h, snap._h, ptr, None if stream is None else C.c_void_p(int(stream)), int(bool(sync))))
+        _check(self._lib.lm_snapshot_restore(self._h, snap._h, ptr, _stream_ptr(stream), int(bool(sync))))
 
     def fork(self, src=None, stream=None, sync=True, mask=None):
         """Environment e continues from the PRESENT state of environment ``src[e]``: a save into a scratch snapshot owned by the batch,

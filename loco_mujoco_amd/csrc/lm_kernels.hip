@@ -77,6 +77,10 @@ struct lm_batch {
   // terminal observations (lm_set_terminal_obs, lm_step.h KArgs::term_obs): the buffer the kernels write (null: off), the one the batch
   // owns (null with a caller's buffer), and the fourth array of every pinned result set, [N][nobs] float64 (lm_pinned_terminal_obs)
   float *term_obs, *term_own; double* h_term64[LM_PINNED_SLOTS];
+  // every device or pinned array above that the batch owns: its field's address, entered by batch_array where the array is allocated.
+  // lm_batch_destroy releases what these fields hold at that moment and names none of them
+  struct Owned { void** field; bool pinned; };
+  std::vector<Owned> owned;
 };
 // A/B switches of the probe builds (tools/probes: `make EXTRA=-DLM_PROBES ...`). The shipped library reads NO environment variable:
 // tests/test_abi_exports.py checks that `getenv` is not among its undefined symbols.
@@ -89,7 +93,39 @@ struct lm_batch {
 static lmk::Family traits(const lm_batch* b) { return lmk::family(b->m->family); }      // (lm_families.h; of a model without a family: all false)
 static bool one_layout_only(const lm_batch* b) { return b->m->family >= 0 && !traits(b).specialised(); }
 
+static bool replicas_off() { static const bool off = LM_PROBE_ENV("LM_NO_REPLICAS") != nullptr; return off; }      // A/B switch
+
 constexpr size_t kLdsAssumed = 160 * 1024;      // LDS of a gfx950 CU (lm_core.h: LaneMem)
+
+// a device allocation that lives for one call: released on every return path
+struct HipFree { void operator()(void* p) const { (void)hipFree(p); } };
+template <class T> using dev_temp = std::unique_ptr<T, HipFree>;
+template <class T> static int dev_temp_alloc(dev_temp<T>* out, size_t count) {
+  T* p = nullptr;
+  HIPCHK(hipMalloc(&p, sizeof(T) * count));
+  out->reset(p);
+  return 0;
+}
+
+// THE allocation of a batch's array: `count` zeroed elements on the device (or in pinned host memory) behind `*field`. What the field
+// held before is released first (arrays that are replaced: the reset table, the variant tables, the staging rows ...); the field is
+// entered into b->owned, so nothing else has to remember it
+static void batch_release(void** field, bool pinned) {
+  if (*field) (void)(pinned ? hipHostFree(*field) : hipFree(*field));
+  *field = nullptr;
+}
+template <class T> static void batch_release(T** field) { batch_release((void**)field, false); }
+template <class T> static int batch_array(lm_batch* b, T** field, size_t count, bool pinned = false) {
+  void** f = (void**)field;
+  batch_release(f, pinned);
+  bool known = false;
+  for (const lm_batch::Owned& o : b->owned) known = known || o.field == f;
+  if (!known) b->owned.push_back({f, pinned});
+  const size_t bytes = sizeof(T) * (count ? count : 1);
+  if (pinned) { HIPCHK(hipHostMalloc(f, bytes, hipHostMallocDefault)); memset(*f, 0, bytes); }
+  else { HIPCHK(hipMalloc(f, bytes)); HIPCHK(hipMemset(*f, 0, bytes)); }
+  return 0;
+}
 
 // the launch functions of the lm_family.hip objects, [family][part]: from the one list of families (absent ids: null)
 static lmk::family_fn kFamilyTable[lmk::LMK_NFAMILY][3];
@@ -139,11 +175,10 @@ static std::string layout_refusal(const lm_batch* b, int epb, bool fwd) {
 // allow one wave per SIMD, and 4096 environments are exactly one wave per SIMD): the step time is the same, 16.0 ms either way.
 // profiles/r5_notes.md §4.)
 template <bool FWD>
-static void launch_variant(lm_batch* b, const KArgs& a) {
-  static const bool no_replicas = LM_PROBE_ENV("LM_NO_REPLICAS") != nullptr;                  // A/B switch
+static void launch_variant(lm_batch* b, const KArgs& a, hipStream_t stream) {
   const int fam = b->m->family;
   if (fam < 0) { g_launch_err = "chains of six links are compiled for Euler, of seven links for RK4 — condim-3 pyramids, no muscles only"; return; }
-  const LaunchCtx L = {b->stream, b->n_active, b->epb, b->m->lds_limit, &g_launch_err, nullptr, 0};
+  const LaunchCtx L = {stream, b->n_active, b->epb, b->m->lds_limit, &g_launch_err, nullptr, 0};
   if (b->n_active <= 0) return;            // an empty active list: nothing to run
   if (b->lds_ok[FWD] != b->epb) {          // (lm_batch_set_layout refuses such a layout; a model's default layout and the forward kernel are checked here, once)
     g_layout_err = layout_refusal(b, b->epb, FWD);
@@ -156,7 +191,7 @@ static void launch_variant(lm_batch* b, const KArgs& a) {
     kFamilyTable[fam][b->m->P.integrator == LM_INT_RK4 ? 1 : 0](L, a, FWD ? lmk::LMK_FWD : lmk::LMK_REP1);      // (its parts: Euler | RK4)
     return;
   }
-  const int kind = lmk::pick_kind(FWD, a.nfused > 1, b->nvar > 0, b->dofprm != nullptr, b->epb <= 4 && !no_replicas);
+  const int kind = lmk::pick_kind(FWD, a.nfused > 1, b->nvar > 0, b->dofprm != nullptr, b->epb <= 4 && !replicas_off());
   const int big = lmk::find_kind(b->nvar > 0 ? 2 : (b->dofprm ? 1 : 0), lmk::kReplay, true);
   const lmk::family_fn launch = kFamilyTable[fam][lmk::kKinds[kind].part], launch_big = kFamilyTable[fam][lmk::kKinds[big].part];
   KArgs r = a;
@@ -204,7 +239,7 @@ static void launch_variant(lm_batch* b, const KArgs& a) {
     g_launch_err = msg;
     if (pollers) {
       (void)hipStreamSynchronize(b->stream2);
-      (void)hipStreamSynchronize(b->stream);
+      (void)hipStreamSynchronize(stream);
       (void)hipMemset(b->replay_ctl, 0, sizeof(int) * 4);
     }
   };
@@ -213,12 +248,12 @@ static void launch_variant(lm_batch* b, const KArgs& a) {
   if (replay) {
     // the drain pass, behind the regular launch AND the pollers: whatever is still listed; resets the control words. An empty
     // list costs a few microseconds (its workgroups read a word and leave)
-    if (pollers && hipStreamWaitEvent(b->stream, b->ev_join, 0) != hipSuccess) { bail("stream join failed"); return; }
+    if (pollers && hipStreamWaitEvent(stream, b->ev_join, 0) != hipSuccess) { bail("stream join failed"); return; }
     r.drain = 1; r.stats_off = 0;
-    const LaunchCtx L3 = {b->stream, b->N, lmk::kReplayGrid, b->m->lds_limit, &g_launch_err, nullptr, 0};
+    const LaunchCtx L3 = {stream, b->N, lmk::kReplayGrid, b->m->lds_limit, &g_launch_err, nullptr, 0};
     if (!launch_big(L3, r, big)) { bail("no replay kernel in the family"); return; }
     if (g_launch_err) { bail(g_launch_err); return; }
-    if (hipEventRecord(b->ev_done[b->epoch & 1], b->stream) != hipSuccess) { bail("event record failed"); return; }
+    if (hipEventRecord(b->ev_done[b->epoch & 1], stream) != hipSuccess) { bail("event record failed"); return; }
     b->epoch++;
   }
 }
@@ -294,39 +329,26 @@ void lm_batch_destroy(lm_batch* b);
 static int batch_alloc(lm_batch* b) {
   lm_model* m = b->m;
   const int N = b->N, nv = m->T.nv;
-  HIPCHK(hipMalloc(&b->qpos, sizeof(float) * nv * N)); HIPCHK(hipMalloc(&b->qvel, sizeof(float) * nv * N));
-  HIPCHK(hipMalloc(&b->warm, sizeof(float) * nv * N)); HIPCHK(hipMalloc(&b->goal, sizeof(float) * 4 * N));
-  HIPCHK(hipMalloc(&b->action, sizeof(float) * m->T.nu * N)); HIPCHK(hipMalloc(&b->obs, sizeof(float) * m->T.nobs * N));
-  HIPCHK(hipMalloc(&b->reward, sizeof(float) * N)); HIPCHK(hipMalloc(&b->done, N));
-  HIPCHK(hipMalloc(&b->flags, N)); HIPCHK(hipMemset(b->flags, 0, N));
-  HIPCHK(hipMalloc(&b->ep_step, sizeof(int) * N)); HIPCHK(hipMalloc(&b->ep_count, sizeof(unsigned) * N));
-  if (m->T.na > 0) { HIPCHK(hipMalloc(&b->act, sizeof(float) * m->T.na * N)); HIPCHK(hipMemset(b->act, 0, sizeof(float) * m->T.na * N)); }
+  const size_t nvN = (size_t)nv * N;
   b->stat_pre_off = b->nblocks; b->nstat = b->nblocks + lmk::kReplayGrid;      // the concurrent replay kernel adds into slots of its own
-  HIPCHK(hipMalloc(&b->stats, sizeof(DevStats) * b->nstat));
+  if (batch_array(b, &b->qpos, nvN) || batch_array(b, &b->qvel, nvN) || batch_array(b, &b->warm, nvN) || batch_array(b, &b->goal, (size_t)4 * N) ||
+      batch_array(b, &b->action, (size_t)m->T.nu * N) || batch_array(b, &b->obs, (size_t)m->T.nobs * N) || batch_array(b, &b->reward, N) ||
+      batch_array(b, &b->done, N) || batch_array(b, &b->flags, N) || batch_array(b, &b->ep_step, N) || batch_array(b, &b->ep_count, N) ||
+      (m->T.na > 0 && batch_array(b, &b->act, (size_t)m->T.na * N)) || batch_array(b, &b->stats, b->nstat) ||
+      batch_array(b, &b->replay_list, N) || batch_array(b, &b->stall, N) || batch_array(b, &b->replay_ctl, 8) || batch_array(b, &b->replay_mark, N) ||
+      batch_array(b, &b->hq, nvN) || batch_array(b, &b->hv, nvN) || batch_array(b, &b->hw, nvN) || batch_array(b, &b->hsub, N) ||
+      batch_array(b, &b->premark, N) || batch_array(b, &b->slack, (size_t)12 * N) ||
+      batch_array(b, &b->timers, 32 + 32 * (size_t)b->nblocks)) return 1;
+#ifdef LM_TIMERS
+  if (batch_array(b, &b->tline, 4 * (size_t)N + 2 * (size_t)b->nblocks)) return 1;
+#endif
   HIPCHK(hipHostMalloc((void**)&b->h_hint, sizeof(int) * 4, hipHostMallocDefault)); b->h_hint[0] = 0; b->h_hint[1] = 0; b->h_hint[2] = 0; b->h_hint[3] = 0;
-  HIPCHK(hipMalloc(&b->replay_list, sizeof(int) * N)); HIPCHK(hipMalloc(&b->stall, sizeof(int) * N)); HIPCHK(hipMalloc(&b->replay_ctl, sizeof(int) * 8));
-  HIPCHK(hipMemset(b->replay_list, 0, sizeof(int) * N)); HIPCHK(hipMemset(b->stall, 0, sizeof(int) * N)); HIPCHK(hipMemset(b->replay_ctl, 0, sizeof(int) * 8));
-  HIPCHK(hipMalloc(&b->replay_mark, N)); HIPCHK(hipMemset(b->replay_mark, 0, N));
-  HIPCHK(hipMalloc(&b->hq, sizeof(float) * nv * N)); HIPCHK(hipMalloc(&b->hv, sizeof(float) * nv * N)); HIPCHK(hipMalloc(&b->hw, sizeof(float) * nv * N));
-  HIPCHK(hipMalloc(&b->hsub, sizeof(int) * N)); HIPCHK(hipMemset(b->hsub, 0, sizeof(int) * N));
-  HIPCHK(hipMalloc(&b->premark, sizeof(int) * N)); HIPCHK(hipMemset(b->premark, 0, sizeof(int) * N));
-  HIPCHK(hipMalloc(&b->slack, sizeof(float) * 12 * N)); HIPCHK(hipMemset(b->slack, 0, sizeof(float) * 12 * N));
   // the convex collider's warm-start cache: one record per environment and geom-pair record of the models whose hull pairs run through
   // it in kernels with five or more links per chain (128 B each: HumanoidTorque 692 pairs -> 88 KB per environment, 363 MB at 4096)
-  b->mprc = nullptr; b->mprc_pairs = 0;
   if (m->d_meshadj && m->n_gpt_floats > 0 && m->T.max_links > 3) {
     b->mprc_pairs = m->n_gpt_floats / LM_GPAIR_SIZE;
-    const size_t bytes = sizeof(float) * lm::kMprCacheFloats * (size_t)b->mprc_pairs * (size_t)N;
-    HIPCHK(hipMalloc(&b->mprc, bytes)); HIPCHK(hipMemset(b->mprc, 0, bytes));
+    if (batch_array(b, &b->mprc, lm::kMprCacheFloats * (size_t)b->mprc_pairs * (size_t)N)) return 1;
   }
-  HIPCHK(hipMemset(b->qpos, 0, sizeof(float) * nv * N)); HIPCHK(hipMemset(b->qvel, 0, sizeof(float) * nv * N));
-  HIPCHK(hipMemset(b->warm, 0, sizeof(float) * nv * N)); HIPCHK(hipMemset(b->goal, 0, sizeof(float) * 4 * N));
-  HIPCHK(hipMemset(b->ep_step, 0, sizeof(int) * N)); HIPCHK(hipMemset(b->ep_count, 0, sizeof(unsigned) * N));
-  HIPCHK(hipMemset(b->stats, 0, sizeof(DevStats) * b->nstat));
-  HIPCHK(hipMalloc(&b->timers, sizeof(unsigned long long) * (32 + 32 * (size_t)b->nblocks))); HIPCHK(hipMemset(b->timers, 0, sizeof(unsigned long long) * (32 + 32 * (size_t)b->nblocks)));
-#ifdef LM_TIMERS
-  HIPCHK(hipMalloc(&b->tline, sizeof(unsigned long long) * (4 * (size_t)N + 2 * (size_t)b->nblocks))); HIPCHK(hipMemset(b->tline, 0, sizeof(unsigned long long) * (4 * (size_t)N + 2 * (size_t)b->nblocks)));
-#endif
   HIPCHK(hipStreamCreate(&b->stream)); HIPCHK(hipStreamCreate(&b->stream2));
   HIPCHK(hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&b->ev_join, hipEventDisableTiming));
   HIPCHK(hipEventCreateWithFlags(&b->ev_done[0], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&b->ev_done[1], hipEventDisableTiming));
@@ -337,9 +359,8 @@ static int batch_alloc(lm_batch* b) {
 int lm_batch_create(lm_model* m, int n_envs, lm_batch** out) {
   if (n_envs <= 0) return fail("n_envs must be positive");
   HIPCHK(hipSetDevice(m->device));
-  lm_batch* b = new lm_batch();
-  memset(b, 0, sizeof(*b));
-  b->m = m; b->N = n_envs; b->n_active = n_envs; b->env_map = nullptr;
+  lm_batch* b = new lm_batch();      // (value-initialised: every field starts as zero)
+  b->m = m; b->N = n_envs; b->n_active = n_envs;
   // Four environments per workgroup: with the replicated layout that is one full wave (4 envs x 4 replicas x 4 chains).
   // Larger batches simply run more workgroups back to back (wider workgroups without replicas were 30-50 % slower at
   // every size, profiles/r1_ab_probes.md); lm_batch_set_layout selects the plain layout.
@@ -406,15 +427,7 @@ void lm_batch_destroy(lm_batch* b) {
   if (!b) return;
   hipSetDevice(b->m->device);
   if (b->stream) hipStreamSynchronize(b->stream);
-  void* bufs[] = {b->qpos, b->qvel, b->warm, b->goal, b->action, b->obs, b->reward, b->done, b->flags, b->ep_step, b->ep_count, b->stats,
-                  b->table, b->act, b->dofprm, b->drspec, b->timers, b->scr, b->scr_idx, b->replay_list, b->replay_ctl, b->stall, b->replay_mark, b->slack, b->mprc, b->env_map, b->hq, b->hv, b->hw, b->hsub, b->premark, b->tline,
-                  b->vrec, b->vgt, b->vgpt, b->var, b->mc_ib, b->mc_db, b->vdirty, b->mc_mask, b->vgen, b->vdraws};
-  for (void* p : bufs) if (p) (void)hipFree(p);
-  if (b->d_perm) (void)hipFree(b->d_perm);
-  if (b->term_own) (void)hipFree(b->term_own);
-  for (int i = 0; i < LM_PINNED_SLOTS; i++) if (b->h_term64[i]) (void)hipHostFree(b->h_term64[i]);
-  if (b->h_act) (void)hipHostFree(b->h_act);
-  for (int i = 0; i < LM_PINNED_SLOTS; i++) if (b->h_out64[i]) (void)hipHostFree(b->h_out64[i]);
+  for (const lm_batch::Owned& o : b->owned) batch_release(o.field, o.pinned);
   if (b->ev0) (void)hipEventDestroy(b->ev0);
   if (b->ev1) (void)hipEventDestroy(b->ev1);
   if (b->ev_ext) (void)hipEventDestroy(b->ev_ext);
@@ -449,12 +462,11 @@ static int mask_indices(lm_batch* b, const uint8_t* mask, int dim, std::vector<i
   const size_t need = (size_t)std::max<size_t>(idx.size(), 1) * (size_t)std::max(dim, 1);
   if (need > b->scr_cap) {
     HIPCHK(hipStreamSynchronize(b->stream));
-    if (b->scr) HIPCHK(hipFree(b->scr));
-    b->scr = nullptr; b->scr_cap = 0;
-    HIPCHK(hipMalloc(&b->scr, sizeof(float) * need));
+    b->scr_cap = 0;
+    if (batch_array(b, &b->scr, need)) return 1;
     b->scr_cap = need;
   }
-  if (!b->scr_idx) HIPCHK(hipMalloc(&b->scr_idx, sizeof(int) * b->N));
+  if (!b->scr_idx && batch_array(b, &b->scr_idx, b->N)) return 1;
   if (!idx.empty()) HIPCHK(hipMemcpyAsync(b->scr_idx, idx.data(), sizeof(int) * idx.size(), hipMemcpyHostToDevice, b->stream));
   HIPCHK(hipStreamSynchronize(b->stream));
   return 0;
@@ -492,6 +504,17 @@ static int upload_soa(lm_batch* b, float* dev, const float* host_aos, int dim, c
   return 0;
 }
 
+// the other direction, [dim][N] on the device -> [N][dim] on the host: wait for the library's stream, then a blocking copy
+static int download_soa(lm_batch* b, const float* dev, float* host_aos, int dim) {
+  const int N = b->N;
+  std::vector<float> soa((size_t)dim * N);
+  HIPCHK(hipStreamSynchronize(b->stream));
+  HIPCHK(hipMemcpy(soa.data(), dev, sizeof(float) * dim * N, hipMemcpyDeviceToHost));
+  for (int e = 0; e < N; e++)
+    for (int d = 0; d < dim; d++) host_aos[(size_t)e * dim + d] = soa[(size_t)d * N + e];
+  return 0;
+}
+
 int lm_set_state(lm_batch* b, const float* qpos, const float* qvel, const uint8_t* mask) {
   HIPCHK(hipSetDevice(b->m->device));
   const int N = b->N, nv = b->m->T.nv, na = b->m->T.na;
@@ -526,15 +549,9 @@ int lm_set_state(lm_batch* b, const float* qpos, const float* qvel, const uint8_
 
 int lm_get_state(lm_batch* b, float* qpos, float* qvel) {
   HIPCHK(hipSetDevice(b->m->device));
-  const int N = b->N, nv = b->m->T.nv;
-  std::vector<float> soa((size_t)nv * N);
-  for (int pass = 0; pass < 2; pass++) {
-    float* dst = pass == 0 ? qpos : qvel;
-    if (!dst) continue;
-    HIPCHK(hipStreamSynchronize(b->stream));
-    HIPCHK(hipMemcpy(soa.data(), pass == 0 ? b->qpos : b->qvel, sizeof(float) * nv * N, hipMemcpyDeviceToHost));
-    for (int e = 0; e < N; e++) for (int d = 0; d < nv; d++) dst[(size_t)e * nv + d] = soa[(size_t)d * N + e];
-  }
+  const int nv = b->m->T.nv;
+  if (qpos && download_soa(b, b->qpos, qpos, nv)) return 1;
+  if (qvel && download_soa(b, b->qvel, qvel, nv)) return 1;
   return 0;
 }
 
@@ -548,7 +565,7 @@ int lm_set_dof_params(lm_batch* b, const float* damping, const float* stiffness,
       return fail("per-environment joint parameters and model variants are not compiled for this model's kernel family (generic kernels)");
     std::vector<float> init((size_t)3 * nv * N);
     for (int p = 0; p < 3; p++) for (int d = 0; d < nv; d++) for (int e = 0; e < N; e++) init[((size_t)p * nv + d) * N + e] = b->m->nominal[(size_t)p * nv + d];
-    HIPCHK(hipMalloc(&b->dofprm, sizeof(float) * 3 * nv * N));
+    if (batch_array(b, &b->dofprm, (size_t)3 * nv * N)) return 1;
     HIPCHK(hipMemcpy(b->dofprm, init.data(), sizeof(float) * 3 * nv * N, hipMemcpyHostToDevice));
   }
   const float* src[3] = {damping, stiffness, frictionloss};
@@ -565,12 +582,10 @@ int lm_get_dof_params(lm_batch* b, float* damping, float* stiffness, float* fric
   HIPCHK(hipSetDevice(b->m->device));
   const int N = b->N, nv = b->m->T.nv;
   float* dst[3] = {damping, stiffness, frictionloss};
-  std::vector<float> soa((size_t)nv * N);
-  HIPCHK(hipStreamSynchronize(b->stream));
   for (int p = 0; p < 3; p++) {
     if (!dst[p]) continue;
-    if (b->dofprm) HIPCHK(hipMemcpy(soa.data(), b->dofprm + (size_t)p * nv * N, sizeof(float) * nv * N, hipMemcpyDeviceToHost));
-    for (int e = 0; e < N; e++) for (int d = 0; d < nv; d++) dst[p][(size_t)e * nv + d] = b->dofprm ? soa[(size_t)d * N + e] : b->m->nominal[(size_t)p * nv + d];
+    if (b->dofprm) { if (download_soa(b, b->dofprm + (size_t)p * nv * N, dst[p], nv)) return 1; continue; }
+    for (int e = 0; e < N; e++) for (int d = 0; d < nv; d++) dst[p][(size_t)e * nv + d] = b->m->nominal[(size_t)p * nv + d];
   }
   return 0;
 }
@@ -578,25 +593,25 @@ int lm_get_dof_params(lm_batch* b, float* damping, float* stiffness, float* fric
 int lm_set_dof_randomization(lm_batch* b, const float* spec) {
   HIPCHK(hipSetDevice(b->m->device));
   const int nv = b->m->T.nv;
-  if (!spec) { if (b->drspec) { (void)hipFree(b->drspec); b->drspec = nullptr; } return 0; }
+  if (!spec) { batch_release(&b->drspec); return 0; }
   for (int i = 0; i < 3 * nv; i++) { const int k = (int)spec[3 * i]; if (k < 0 || k > 3) return fail("bad randomisation kind"); }
   if (!b->dofprm && lm_set_dof_params(b, nullptr, nullptr, nullptr, nullptr)) return 1;
-  if (!b->drspec) HIPCHK(hipMalloc(&b->drspec, sizeof(float) * 9 * nv));
+  if (!b->drspec && batch_array(b, &b->drspec, (size_t)9 * nv)) return 1;
   HIPCHK(hipMemcpy(b->drspec, spec, sizeof(float) * 9 * nv, hipMemcpyHostToDevice));
   return 0;
 }
 
-static void compile_models(lm_batch* b, const unsigned char* mask, int all);
+static void compile_models(lm_batch* b, const unsigned char* mask, int all, hipStream_t stream);
 
 int lm_set_model_variants(lm_batch* b, const float* records, const float* geom_tables, const float* pair_tables,
                           int pair_floats, int n_variants) {
   HIPCHK(hipSetDevice(b->m->device));
   HIPCHK(hipStreamSynchronize(b->stream));
-  for (float** p : {&b->vrec, &b->vgt, &b->vgpt}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+  for (float** p : {&b->vrec, &b->vgt, &b->vgpt}) batch_release(p);
   b->nvar = 0; b->gpt_floats = 0;
-  if (b->mc_ib) { (void)hipFree(b->mc_ib); (void)hipFree(b->mc_db); b->mc_ib = nullptr; b->mc_db = nullptr; }      // a pool replaces the compiler
+  batch_release(&b->mc_ib); batch_release(&b->mc_db);      // a pool replaces the compiler
   if (n_variants <= 0) {       // pool removed: the joint-parameter rows go with it when this call had created them
-    if (b->dofprm_of_variants && b->dofprm && !b->drspec) { (void)hipFree(b->dofprm); b->dofprm = nullptr; }
+    if (b->dofprm_of_variants && !b->drspec) batch_release(&b->dofprm);
     b->dofprm_of_variants = false;
     return 0;
   }
@@ -608,10 +623,11 @@ int lm_set_model_variants(lm_batch* b, const float* records, const float* geom_t
     b->dofprm_of_variants = true;
   }
   const size_t nr = (size_t)n_variants * LM_IR_SIZE * LM_NCHAIN, ng = (size_t)n_variants * LM_GT_SIZE, np_ = (size_t)n_variants * pair_floats;
-  HIPCHK(hipMalloc(&b->vrec, sizeof(float) * nr)); HIPCHK(hipMemcpy(b->vrec, records, sizeof(float) * nr, hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc(&b->vgt, sizeof(float) * ng)); HIPCHK(hipMemcpy(b->vgt, geom_tables, sizeof(float) * ng, hipMemcpyHostToDevice));
-  if (pair_tables) { HIPCHK(hipMalloc(&b->vgpt, sizeof(float) * np_)); HIPCHK(hipMemcpy(b->vgpt, pair_tables, sizeof(float) * np_, hipMemcpyHostToDevice)); }
-  if (!b->var) HIPCHK(hipMalloc(&b->var, sizeof(int) * b->N));
+  if (batch_array(b, &b->vrec, nr) || batch_array(b, &b->vgt, ng) || (pair_tables && batch_array(b, &b->vgpt, np_))) return 1;
+  HIPCHK(hipMemcpy(b->vrec, records, sizeof(float) * nr, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(b->vgt, geom_tables, sizeof(float) * ng, hipMemcpyHostToDevice));
+  if (pair_tables) HIPCHK(hipMemcpy(b->vgpt, pair_tables, sizeof(float) * np_, hipMemcpyHostToDevice));
+  if (!b->var && batch_array(b, &b->var, b->N)) return 1;
   HIPCHK(hipMemset(b->var, 0, sizeof(int) * b->N));
   HIPCHK(hipMemset(b->slack, 0, sizeof(float) * 12 * b->N));
   b->nvar = n_variants; b->gpt_floats = pair_floats;
@@ -702,30 +718,26 @@ int lm_set_model_compiler(lm_batch* b, const int32_t* index, long long n_index, 
   }
   const int N = b->N;
   const size_t nr = (size_t)LM_IR_SIZE * LM_NCHAIN, ng = (size_t)LM_GT_SIZE, np_ = (size_t)(pair_table ? pair_floats : 0);
-  float* nominal = nullptr;
-  HIPCHK(hipMalloc(&nominal, sizeof(float) * (nr + ng + np_)));
+  dev_temp<float> nominal_tmp;      // the nominal tables on the device, for this call
+  if (dev_temp_alloc(&nominal_tmp, nr + ng + np_)) return 1;
+  float* nominal = nominal_tmp.get();
   HIPCHK(hipMemcpy(nominal, record, sizeof(float) * nr, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(nominal + nr, geom_table, sizeof(float) * ng, hipMemcpyHostToDevice));
   if (np_) HIPCHK(hipMemcpy(nominal + nr + ng, pair_table, sizeof(float) * np_, hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc(&b->vrec, sizeof(float) * nr * N)); HIPCHK(hipMalloc(&b->vgt, sizeof(float) * ng * N));
-  if (np_) HIPCHK(hipMalloc(&b->vgpt, sizeof(float) * np_ * N));
+  if (batch_array(b, &b->vrec, nr * N) || batch_array(b, &b->vgt, ng * N) || (np_ && batch_array(b, &b->vgpt, np_ * N))) return 1;
   lmc::replicate(b->vrec, nominal, (long long)nr, N, b->stream);
   lmc::replicate(b->vgt, nominal + nr, (long long)ng, N, b->stream);
   if (np_) lmc::replicate(b->vgpt, nominal + nr + ng, (long long)np_, N, b->stream);
-  if (!b->var) HIPCHK(hipMalloc(&b->var, sizeof(int) * N));
+  if (!b->var && batch_array(b, &b->var, N)) return 1;
   lmc::iota(b->var, N, b->stream);
-  HIPCHK(hipMalloc(&b->mc_ib, sizeof(int) * n_index)); HIPCHK(hipMemcpy(b->mc_ib, index, sizeof(int) * n_index, hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc(&b->mc_db, sizeof(double) * n_data)); HIPCHK(hipMemcpy(b->mc_db, data, sizeof(double) * n_data, hipMemcpyHostToDevice));
-  for (void** p : {(void**)&b->vdirty, (void**)&b->mc_mask, (void**)&b->vgen, (void**)&b->vdraws}) if (*p) { (void)hipFree(*p); *p = nullptr; }
-  HIPCHK(hipMalloc(&b->vdirty, N)); HIPCHK(hipMemset(b->vdirty, 0, N));
-  HIPCHK(hipMalloc(&b->mc_mask, N));
-  HIPCHK(hipMalloc(&b->vgen, sizeof(unsigned) * N)); HIPCHK(hipMemset(b->vgen, 0, sizeof(unsigned) * N));
-  HIPCHK(hipMalloc(&b->vdraws, sizeof(double) * (size_t)N * nd));
+  if (batch_array(b, &b->mc_ib, (size_t)n_index) || batch_array(b, &b->mc_db, (size_t)n_data) || batch_array(b, &b->vdirty, N) ||
+      batch_array(b, &b->mc_mask, N) || batch_array(b, &b->vgen, N) || batch_array(b, &b->vdraws, (size_t)N * nd)) return 1;
+  HIPCHK(hipMemcpy(b->mc_ib, index, sizeof(int) * n_index, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(b->mc_db, data, sizeof(double) * n_data, hipMemcpyHostToDevice));
   b->mc_ndraw = nd; b->mc_seed = seed; b->nvar = N; b->gpt_floats = (int)np_; b->var_rows = 0;
-  compile_models(b, nullptr, 1);                       // every environment starts on a model of its own
+  compile_models(b, nullptr, 1, b->stream);            // every environment starts on a model of its own
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(b->stream));
-  HIPCHK(hipFree(nominal));
   return 0;
 }
 
@@ -733,7 +745,7 @@ int lm_compile_models(lm_batch* b, const uint8_t* mask) {
   HIPCHK(hipSetDevice(b->m->device));
   if (!b->mc_ib) return fail("the batch has no model compiler (lm_set_model_compiler)");
   if (mask) HIPCHK(hipMemcpyAsync(b->mc_mask, mask, b->N, hipMemcpyHostToDevice, b->stream));
-  compile_models(b, mask ? b->mc_mask : nullptr, mask ? 0 : 1);
+  compile_models(b, mask ? b->mc_mask : nullptr, mask ? 0 : 1, b->stream);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(b->stream));
   return 0;
@@ -770,12 +782,7 @@ int lm_set_activation(lm_batch* b, const float* act, const uint8_t* mask) {
 int lm_get_activation(lm_batch* b, float* act) {
   HIPCHK(hipSetDevice(b->m->device));
   if (!b->act) return fail("model has no activation states");
-  const int N = b->N, na = b->m->T.na;
-  std::vector<float> soa((size_t)na * N);
-  HIPCHK(hipStreamSynchronize(b->stream));
-  HIPCHK(hipMemcpy(soa.data(), b->act, sizeof(float) * na * N, hipMemcpyDeviceToHost));
-  for (int e = 0; e < N; e++) for (int d = 0; d < na; d++) act[(size_t)e * na + d] = soa[(size_t)d * N + e];
-  return 0;
+  return download_soa(b, b->act, act, b->m->T.na);
 }
 
 int lm_set_goal(lm_batch* b, const float* goal, const uint8_t* mask) {
@@ -812,21 +819,83 @@ static KArgs make_args(lm_batch* b) {
   return a;
 }
 
-static void compile_models(lm_batch* b, const unsigned char* mask, int all) {
+static void compile_models(lm_batch* b, const unsigned char* mask, int all, hipStream_t stream) {
   lmc::Args c;
   c.ib = b->mc_ib; c.db = b->mc_db; c.N = b->N; c.seed = b->mc_seed; c.env_offset = b->env_offset; c.dirty = b->vdirty; c.mask = mask; c.all = all;
   c.gen = b->vgen; c.vrec = b->vrec; c.vgt = b->vgt; c.vgpt = b->vgpt; c.gpt_floats = b->gpt_floats; c.slack = b->slack; c.draws = b->vdraws;
-  lmc::launch(c, b->stream);
+  lmc::launch(c, stream);
 }
 
-static void launch_step(lm_batch* b, const KArgs& a) {
-  // the per-thread HIP error state is shared with whoever else uses HIP in this process (PyTorch probes peers, pointer
-  // attributes ...): drop what they left behind so that the check after the launch reports OUR launch
-  (void)hipGetLastError();
-  g_launch_err = nullptr;
-  launch_variant<false>(b, a);
-  // the environments that restarted an episode in this launch get their fresh model before the next one (stream order)
-  if (b->mc_ib && b->auto_reset && b->table_rows > 0) compile_models(b, nullptr, 0);
+// The stream an entry point works on: the caller's (e.g. torch's current stream) or, for null, the library's own. enter() orders it
+// behind everything the batch has in flight: the library's stream (ev_ext), and the last launch with a replay pass wherever it ran — its
+// drain pass waits for the pollers of stream2 (ev_join) and is followed by ev_done, so that event also covers a launch that another
+// caller's stream still holds. leave() orders the library's stream behind the stream in use, so that whatever the library queues next
+// (lm_get_state, lm_get_stats, lm_rollout ...) waits for this call's work; an entry point that returns early leaves through the destructor
+struct StreamScope {
+  lm_batch* b; hipStream_t used; bool entered = false;
+  StreamScope(lm_batch* b_, void* stream) : b(b_), used(stream ? (hipStream_t)stream : b_->stream) {}
+  StreamScope(const StreamScope&) = delete;
+  int enter() {
+    if (b->epoch > 0) HIPCHK(hipStreamWaitEvent(used, b->ev_done[(b->epoch - 1) & 1], 0));
+    if (used != b->stream) { HIPCHK(hipEventRecord(b->ev_ext, b->stream)); HIPCHK(hipStreamWaitEvent(used, b->ev_ext, 0)); }
+    entered = true;
+    return 0;
+  }
+  int leave() {
+    if (!entered) return 0;
+    entered = false;
+    if (used != b->stream) { HIPCHK(hipEventRecord(b->ev_ext, used)); HIPCHK(hipStreamWaitEvent(b->stream, b->ev_ext, 0)); }
+    return 0;
+  }
+  ~StreamScope() { (void)leave(); }
+};
+
+// Where the control steps of one call take their actions and leave their results: the first step's pointer and the stride from one
+// control step to the next, in elements (0: every step at the same rows). `action_mode` is the kernels' (0: `action`, 1: zero, 2:
+// uniform random); `seed` keys the random actions and the restarts; `term` null: the buffer of lm_set_terminal_obs, if any
+struct StepIO {
+  int action_mode; unsigned long long seed;
+  const float* action; long long action_stride;
+  float* obs; long long obs_stride;
+  float* reward; long long reward_stride;
+  unsigned char* done; long long done_stride;
+  float* term; long long term_stride;
+};
+// the batch's own rows, overwritten by every control step: what lm_step* and the policy-free rollouts write
+static StepIO own_rows(lm_batch* b, int action_mode, const float* action) {
+  return {action_mode, b->seed, action, 0, b->obs, 0, b->reward, 0, b->done, 0, nullptr, 0};
+}
+
+// THE launch path of lm_step*, lm_rollout_fused and lm_rollout_tape: queues `n_steps` control steps on `stream`, `steps_per_launch` of
+// them per launch. b->step_index, the count that keys the random actions, advances by the launches that were accepted and by no
+// other: a refused call leaves it where it was. `timed`: ev0 / ev1 around the span
+static int queue_steps(lm_batch* b, hipStream_t stream, const StepIO& io, int n_steps, int steps_per_launch, bool timed) {
+  // one control step per launch where there is no fused kernel (the full-wave layout, the generic family), and with the model compiler:
+  // a restart inside a launch needs its fresh model before the episode's first step. The launch's pointers then carry the offsets
+  if (b->epb > 4 || replicas_off() || one_layout_only(b) || b->mc_ib) steps_per_launch = 1;
+  KArgs a = make_args(b);
+  a.action_mode = io.action_mode; a.seed = io.seed;
+  a.tape_action = io.action_stride; a.tape_obs = io.obs_stride; a.tape_reward = io.reward_stride; a.tape_done = io.done_stride; a.tape_term = io.term_stride;
+  if (timed) HIPCHK(hipEventRecord(b->ev0, stream));
+  for (int s = 0; s < n_steps; s += steps_per_launch) {
+    a.nfused = (n_steps - s < steps_per_launch) ? n_steps - s : steps_per_launch;
+    a.step_index = b->step_index;
+    a.action = io.action ? io.action + s * io.action_stride : nullptr;
+    a.obs = io.obs + s * io.obs_stride; a.reward = io.reward + s * io.reward_stride; a.done = io.done + s * io.done_stride;
+    if (io.term) a.term_obs = io.term + s * io.term_stride;
+    // the per-thread HIP error state is shared with whoever else uses HIP in this process (PyTorch probes peers, pointer
+    // attributes ...): drop what they left behind so that the check after the launch reports OUR launch
+    (void)hipGetLastError();
+    g_launch_err = nullptr;
+    launch_variant<false>(b, a, stream);
+    if (g_launch_err) return fail(g_launch_err);
+    // the environments that restarted an episode in this launch get their fresh model before the next one (stream order)
+    if (b->mc_ib && b->auto_reset && b->table_rows > 0) compile_models(b, nullptr, 0, stream);
+    HIPCHK(hipGetLastError());
+    b->step_index += (unsigned)a.nfused;
+  }
+  if (timed) HIPCHK(hipEventRecord(b->ev1, stream));
+  return 0;
 }
 
 static int drain_stats(lm_batch* b) {
@@ -846,7 +915,7 @@ static int drain_stats(lm_batch* b) {
 int lm_batch_set_active(lm_batch* b, const int32_t* env_ids, int count) {
   HIPCHK(hipSetDevice(b->m->device));
   HIPCHK(hipStreamSynchronize(b->stream));
-  if (!env_ids) { b->n_active = b->N; if (b->env_map) { HIPCHK(hipFree(b->env_map)); b->env_map = nullptr; } return 0; }
+  if (!env_ids) { b->n_active = b->N; batch_release(&b->env_map); return 0; }
   if (traits(b).no_active_lists()) return fail("active lists are not compiled into the quadruped's kernels (lm_step.h: the indirection costs the bench kernel 0.9 %)");
   if (count < 0 || count > b->N) return fail("active list: more entries than environments");
   std::vector<char> seen((size_t)b->N, 0);
@@ -855,7 +924,7 @@ int lm_batch_set_active(lm_batch* b, const int32_t* env_ids, int count) {
     if (seen[env_ids[i]]) return fail("active list: an environment is listed twice");
     seen[env_ids[i]] = 1;
   }
-  if (!b->env_map) HIPCHK(hipMalloc(&b->env_map, sizeof(int) * (size_t)b->N));
+  if (!b->env_map && batch_array(b, &b->env_map, (size_t)b->N)) return 1;
   if (count > 0) HIPCHK(hipMemcpy(b->env_map, env_ids, sizeof(int) * (size_t)count, hipMemcpyHostToDevice));
   b->n_active = count;
   return 0;
@@ -877,14 +946,8 @@ int lm_lds_bytes(int family, int kind, int envs_per_workgroup, int cm_used_float
 int lm_step(lm_batch* b, const float* action, float* obs, float* reward, uint8_t* done) {
   HIPCHK(hipSetDevice(b->m->device));
   const int N = b->N; const Task& T = b->m->T;
-  KArgs a = make_args(b);
-  if (action) { HIPCHK(hipMemcpyAsync(b->action, action, sizeof(float) * T.nu * N, hipMemcpyHostToDevice, b->stream)); a.action = b->action; a.action_mode = 0; }
-  else a.action_mode = 1;
-  a.obs = b->obs; a.reward = b->reward; a.done = b->done;
-  launch_step(b, a);
-  if (g_launch_err) return fail(g_launch_err);
-  HIPCHK(hipGetLastError());
-  b->step_index++;
+  if (action) HIPCHK(hipMemcpyAsync(b->action, action, sizeof(float) * T.nu * N, hipMemcpyHostToDevice, b->stream));
+  if (queue_steps(b, b->stream, own_rows(b, action ? 0 : 1, action ? b->action : nullptr), 1, 1, false)) return 1;
   if (obs) HIPCHK(hipMemcpyAsync(obs, b->obs, sizeof(float) * T.nobs * N, hipMemcpyDeviceToHost, b->stream));
   if (reward) HIPCHK(hipMemcpyAsync(reward, b->reward, sizeof(float) * N, hipMemcpyDeviceToHost, b->stream));
   if (done) HIPCHK(hipMemcpyAsync(done, b->done, N, hipMemcpyDeviceToHost, b->stream));
@@ -923,11 +986,7 @@ __global__ void pack_out64_term_kernel(const float* __restrict__ obs, const floa
 // the fourth array of the pinned result sets (allocated when both the ring and the terminal observations are in use)
 static int pinned_term_alloc(lm_batch* b) {
   if (b->h_term64[0]) return 0;
-  const size_t bytes = sizeof(double) * (size_t)b->N * (size_t)b->m->T.nobs;
-  for (int i = 0; i < LM_PINNED_SLOTS; i++) {
-    HIPCHK(hipHostMalloc((void**)&b->h_term64[i], bytes, hipHostMallocDefault));
-    memset(b->h_term64[i], 0, bytes);
-  }
+  for (int i = 0; i < LM_PINNED_SLOTS; i++) if (batch_array(b, &b->h_term64[i], (size_t)b->N * (size_t)b->m->T.nobs, true)) return 1;
   return 0;
 }
 
@@ -935,11 +994,8 @@ static int pinned_alloc(lm_batch* b) {
   if (b->h_act) return 0;
   const size_t N = (size_t)b->N, nobs = (size_t)b->m->T.nobs;
   b->out64_bytes = sizeof(double) * (N * nobs + N) + N;
-  HIPCHK(hipHostMalloc((void**)&b->h_act, sizeof(float) * N * (size_t)b->m->T.nu, hipHostMallocDefault));
-  for (int i = 0; i < LM_PINNED_SLOTS; i++) {
-    HIPCHK(hipHostMalloc((void**)&b->h_out64[i], b->out64_bytes, hipHostMallocDefault));
-    memset(b->h_out64[i], 0, b->out64_bytes);
-  }
+  if (batch_array(b, &b->h_act, N * (size_t)b->m->T.nu, true)) return 1;
+  for (int i = 0; i < LM_PINNED_SLOTS; i++) if (batch_array(b, &b->h_out64[i], b->out64_bytes, true)) return 1;
   return 0;
 }
 
@@ -966,7 +1022,7 @@ int lm_set_terminal_obs(lm_batch* b, int enabled, float* d_out) {
   // [n_envs][nobs] float32 on this batch's device is the caller's promise, the library cannot check it
   if (d_out) { b->term_obs = d_out; return 0; }
   const size_t bytes = sizeof(float) * (size_t)b->N * (size_t)b->m->T.nobs;
-  if (!b->term_own) HIPCHK(hipMalloc(&b->term_own, bytes));
+  if (!b->term_own && batch_array(b, &b->term_own, (size_t)b->N * (size_t)b->m->T.nobs)) return 1;
   HIPCHK(hipMemsetAsync(b->term_own, 0, bytes, b->stream));
   HIPCHK(hipStreamSynchronize(b->stream));
   b->term_obs = b->term_own;
@@ -996,12 +1052,12 @@ int lm_pinned_terminal_obs(lm_batch* b, int slot, double** term_obs) {
 
 int lm_set_obs_order(lm_batch* b, const int32_t* perm, int n) {
   HIPCHK(hipSetDevice(b->m->device));
-  if (b->d_perm) { HIPCHK(hipStreamSynchronize(b->stream)); HIPCHK(hipFree(b->d_perm)); b->d_perm = nullptr; }
+  if (b->d_perm) { HIPCHK(hipStreamSynchronize(b->stream)); batch_release(&b->d_perm); }
   if (!perm) return 0;
   const int nobs = b->m->T.nobs;
   if (n != nobs) return fail("observation order: one entry per observation column");
   for (int j = 0; j < n; j++) if (perm[j] < 0 || perm[j] >= nobs) return fail("observation order: column out of range");
-  HIPCHK(hipMalloc(&b->d_perm, sizeof(int) * n));
+  if (batch_array(b, &b->d_perm, (size_t)n)) return 1;
   HIPCHK(hipMemcpy(b->d_perm, perm, sizeof(int) * n, hipMemcpyHostToDevice));
   return 0;
 }
@@ -1015,16 +1071,10 @@ int lm_step_pinned(lm_batch* b, const double* action, int slot) {
   const int N = b->N; const Task& T = b->m->T;
   const size_t na = (size_t)N * T.nu;
   for (size_t i = 0; i < na; i++) b->h_act[i] = (float)action[i];
-  KArgs a = make_args(b);
   // the step kernel reads the action out of the pinned staging buffer itself and the conversion kernel writes the pinned slot itself
   // (both mapped into the device's address space): no copy is queued on either side of the launch. Measured on one box against an
   // H2D copy in front and a D2H copy behind (tools/probes/r6/surface.py, 4096 quadrupeds): 1.258 against 1.274 ms per LocoEnv.step()
-  a.action = b->h_act;
-  a.action_mode = 0;
-  a.obs = b->obs; a.reward = b->reward; a.done = b->done;
-  launch_step(b, a);
-  if (g_launch_err) return fail(g_launch_err);
-  b->step_index++;
+  if (queue_steps(b, b->stream, own_rows(b, 0, b->h_act), 1, 1, false)) return 1;
   double* o64 = reinterpret_cast<double*>(b->h_out64[slot]);
   const int total = N * T.nobs, threads = 256;
   if (b->term_obs)
@@ -1040,23 +1090,13 @@ int lm_step_pinned(lm_batch* b, const double* action, int slot) {
 
 int lm_step_device(lm_batch* b, const float* d_action, float* d_obs, float* d_reward, uint8_t* d_done, void* stream, int sync) {
   HIPCHK(hipSetDevice(b->m->device));
-  KArgs a = make_args(b);
-  if (d_action) { a.action = d_action; a.action_mode = 0; } else a.action_mode = 1;
-  a.obs = d_obs ? d_obs : b->obs; a.reward = d_reward ? d_reward : b->reward; a.done = d_done ? d_done : b->done;
-  hipStream_t own = b->stream;
-  hipStream_t used = stream ? (hipStream_t)stream : own;       // the caller's stream (e.g. torch's current stream)
-  // a launch on a foreign stream is ordered on BOTH sides against the library's own stream: it waits for what the
-  // library has queued (state uploads, earlier steps), and whatever the library queues next (lm_get_state, lm_get_stats,
-  // lm_rollout ...) waits for it
-  if (used != own) { HIPCHK(hipEventRecord(b->ev_ext, own)); HIPCHK(hipStreamWaitEvent(used, b->ev_ext, 0)); }
-  b->stream = used;
-  launch_step(b, a);
-  b->stream = own;
-  if (g_launch_err) return fail(g_launch_err);
-  HIPCHK(hipGetLastError());
-  if (used != own) { HIPCHK(hipEventRecord(b->ev_ext, used)); HIPCHK(hipStreamWaitEvent(own, b->ev_ext, 0)); }
-  b->step_index++;
-  if (sync) HIPCHK(hipStreamSynchronize(used));
+  StepIO io = own_rows(b, d_action ? 0 : 1, d_action);
+  if (d_obs) io.obs = d_obs;
+  if (d_reward) io.reward = d_reward;
+  if (d_done) io.done = d_done;
+  StreamScope scope(b, stream);
+  if (scope.enter() || queue_steps(b, scope.used, io, 1, 1, false) || scope.leave()) return 1;
+  if (sync) HIPCHK(hipStreamSynchronize(scope.used));
   return 0;
 }
 
@@ -1065,8 +1105,7 @@ int lm_set_reset_table(lm_batch* b, const float* rows, int n_rows, uint64_t seed
   const Task& T = b->m->T;
   const size_t w = 2 * T.nv + T.ngoal;
   if (n_rows <= 0) return fail("empty reset table");
-  if (b->table) { HIPCHK(hipFree(b->table)); b->table = nullptr; }
-  HIPCHK(hipMalloc(&b->table, sizeof(float) * w * n_rows));
+  if (batch_array(b, &b->table, w * n_rows)) return 1;
   HIPCHK(hipMemcpy(b->table, rows, sizeof(float) * w * n_rows, hipMemcpyHostToDevice));
   b->table_rows = n_rows; b->seed = seed; b->env_offset = global_env_offset;
   b->var_rows = 0;                 // a new table: the variant no longer follows the row until lm_set_variant_rows says so
@@ -1083,22 +1122,9 @@ int lm_rollout_fused(lm_batch* b, int n_steps, int steps_per_launch, int action_
   HIPCHK(hipSetDevice(b->m->device));
   if (action_mode != 0 && action_mode != 1) return fail("action_mode must be 0 (zero) or 1 (uniform random)");
   if (steps_per_launch < 1) return fail("steps_per_launch must be >= 1");
-  static const bool no_replicas = LM_PROBE_ENV("LM_NO_REPLICAS") != nullptr;
-  if (b->epb > 4 || no_replicas || one_layout_only(b)) steps_per_launch = 1;     // no fused kernels for the full-wave layout
-  if (b->mc_ib) steps_per_launch = 1;       // a restart inside a launch needs its fresh model before the episode's first step
-  KArgs a = make_args(b);
-  a.action = nullptr; a.action_mode = action_mode == 0 ? 1 : 2;   // kernel: 1 = zero action, 2 = random
-  a.seed = b->seed ^ (seed * 0x9E3779B97F4A7C15ull);
-  a.obs = b->obs; a.reward = b->reward; a.done = b->done;
-  HIPCHK(hipEventRecord(b->ev0, b->stream));
-  for (int s = 0; s < n_steps; s += steps_per_launch) {
-    a.nfused = (n_steps - s < steps_per_launch) ? n_steps - s : steps_per_launch;
-    a.step_index = b->step_index; b->step_index += (unsigned)a.nfused;
-    launch_step(b, a);
-    if (g_launch_err) return fail(g_launch_err);
-  }
-  HIPCHK(hipEventRecord(b->ev1, b->stream));
-  HIPCHK(hipGetLastError());
+  StepIO io = own_rows(b, action_mode == 0 ? 1 : 2, nullptr);   // kernel: 1 = zero action, 2 = random
+  io.seed = b->seed ^ (seed * 0x9E3779B97F4A7C15ull);
+  if (queue_steps(b, b->stream, io, n_steps, steps_per_launch, true)) return 1;
   HIPCHK(hipEventSynchronize(b->ev1));
   float ms = 0;
   HIPCHK(hipEventElapsedTime(&ms, b->ev0, b->ev1));
@@ -1119,35 +1145,16 @@ int lm_rollout_tape(lm_batch* b, int n_steps, int steps_per_launch, const float*
   if (!d_actions) return fail("lm_rollout_tape: d_actions is null (policy-free rollouts: lm_rollout_fused)");
   if (action_step_stride != 0 && action_step_stride != N * T.nu) return fail("lm_rollout_tape: action_step_stride must be n_envs * nu (a tape) or 0 (action repeat)");
   if (d_term && !b->term_obs) return fail("lm_rollout_tape: d_term needs terminal observations enabled (lm_set_terminal_obs)");
-  static const bool no_replicas = LM_PROBE_ENV("LM_NO_REPLICAS") != nullptr;
-  // as in lm_rollout_fused: one control step per launch where there is no fused kernel (the launch's pointers then carry the offsets)
-  if (b->epb > 4 || no_replicas || one_layout_only(b)) steps_per_launch = 1;
-  if (b->mc_ib) steps_per_launch = 1;
-  KArgs a = make_args(b);            // the batch's own seed: a tape launch restarts episodes exactly like lm_step*
-  a.action_mode = 0;
-  a.tape_action = action_step_stride;
-  // a tape that is not given: the batch's own rows as in lm_step_device, stride 0 — every control step overwrites them
-  a.tape_obs = d_obs ? N * T.nobs : 0; a.tape_reward = d_reward ? N : 0; a.tape_done = d_done ? N : 0; a.tape_term = d_term ? N * T.nobs : 0;
-  hipStream_t own = b->stream;
-  hipStream_t used = stream ? (hipStream_t)stream : own;
-  if (used != own) { HIPCHK(hipEventRecord(b->ev_ext, own)); HIPCHK(hipStreamWaitEvent(used, b->ev_ext, 0)); }
-  HIPCHK(hipEventRecord(b->ev0, used));
-  b->stream = used;
-  for (int s = 0; s < n_steps; s += steps_per_launch) {
-    a.nfused = (n_steps - s < steps_per_launch) ? n_steps - s : steps_per_launch;
-    a.step_index = b->step_index; b->step_index += (unsigned)a.nfused;
-    a.action = d_actions + (long long)s * action_step_stride;
-    a.obs = d_obs ? d_obs + (long long)s * N * T.nobs : b->obs;
-    a.reward = d_reward ? d_reward + (long long)s * N : b->reward;
-    a.done = d_done ? d_done + (long long)s * N : b->done;
-    if (d_term) a.term_obs = d_term + (long long)s * N * T.nobs;
-    launch_step(b, a);
-    if (g_launch_err) { b->stream = own; return fail(g_launch_err); }
-  }
-  b->stream = own;
-  HIPCHK(hipEventRecord(b->ev1, used));
-  HIPCHK(hipGetLastError());
-  if (used != own) { HIPCHK(hipEventRecord(b->ev_ext, used)); HIPCHK(hipStreamWaitEvent(own, b->ev_ext, 0)); }
+  // the batch's own seed: a tape launch restarts episodes exactly like lm_step*. A tape that is not given: the batch's own rows as in
+  // lm_step_device, stride 0 — every control step overwrites them
+  StepIO io = own_rows(b, 0, d_actions);
+  io.action_stride = action_step_stride;
+  if (d_obs) { io.obs = d_obs; io.obs_stride = N * T.nobs; }
+  if (d_reward) { io.reward = d_reward; io.reward_stride = N; }
+  if (d_done) { io.done = d_done; io.done_stride = N; }
+  if (d_term) { io.term = d_term; io.term_stride = N * T.nobs; }
+  StreamScope scope(b, stream);
+  if (scope.enter() || queue_steps(b, scope.used, io, n_steps, steps_per_launch, true) || scope.leave()) return 1;
   if (!sync) return 0;
   HIPCHK(hipEventSynchronize(b->ev1));
   float ms = 0;
@@ -1171,15 +1178,16 @@ int lm_forward_debug(lm_batch* b, const float* action, lm_forward_out* out) {
   a.stats = nullptr; a.replay_list = nullptr;
   if (action) { HIPCHK(hipMemcpy(b->action, action, sizeof(float) * T.nu * N, hipMemcpyHostToDevice)); a.action = b->action; a.action_mode = 0; }
   else a.action_mode = 1;
-  float* buf; int* ibuf;
   const size_t per = (size_t)nv * nv + 5 * nv;
-  HIPCHK(hipMalloc(&buf, sizeof(float) * per * N)); HIPCHK(hipMalloc(&ibuf, sizeof(int) * 2 * N));
+  dev_temp<float> buf_tmp; dev_temp<int> ibuf_tmp;      // the stage outputs on the device, for this call
+  if (dev_temp_alloc(&buf_tmp, per * N) || dev_temp_alloc(&ibuf_tmp, (size_t)2 * N)) return 1;
+  float* buf = buf_tmp.get(); int* ibuf = ibuf_tmp.get();
   HIPCHK(hipMemset(buf, 0, sizeof(float) * per * N));
   a.dM = buf; a.dbias = buf + (size_t)nv * nv * N; a.dsmooth = a.dbias + (size_t)nv * N; a.dqacc_smooth = a.dsmooth + (size_t)nv * N;
   a.dqacc = a.dqacc_smooth + (size_t)nv * N; a.dqfrc = a.dqacc + (size_t)nv * N; a.dncon = ibuf; a.diter = ibuf + N;
   (void)hipGetLastError();
   g_launch_err = nullptr;
-  launch_variant<true>(b, a);
+  launch_variant<true>(b, a, b->stream);
   if (g_launch_err) return fail(g_launch_err);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(b->stream));
@@ -1188,7 +1196,6 @@ int lm_forward_debug(lm_batch* b, const float* action, lm_forward_out* out) {
       get(out->qacc_smooth, a.dqacc_smooth, (size_t)nv * N) || get(out->qacc, a.dqacc, (size_t)nv * N) || get(out->qfrc_constraint, a.dqfrc, (size_t)nv * N)) return 1;
   if (out->ncon) HIPCHK(hipMemcpy(out->ncon, a.dncon, sizeof(int) * N, hipMemcpyDeviceToHost));
   if (out->solver_iter) HIPCHK(hipMemcpy(out->solver_iter, a.diter, sizeof(int) * N, hipMemcpyDeviceToHost));
-  HIPCHK(hipFree(buf)); HIPCHK(hipFree(ibuf));
   return 0;
 }
 
@@ -1326,23 +1333,6 @@ static int snap_check(const lm_batch* b, const int* sig, const char* who, const 
   return 0;
 }
 
-// the stream a snapshot operation runs on, ordered behind everything the batch has in flight: the library's own stream (ev_ext, as in
-// lm_rollout_tape), and the last launch with a replay pass wherever it ran — its drain pass waits for the pollers of stream2 (ev_join)
-// and is followed by ev_done, so that event also covers lm_step_device(sync = 0) on ANOTHER caller's stream
-static int snap_enter(lm_batch* b, void* stream, hipStream_t* used_out) {
-  hipStream_t own = b->stream, used = stream ? (hipStream_t)stream : own;
-  if (b->epoch > 0) HIPCHK(hipStreamWaitEvent(used, b->ev_done[(b->epoch - 1) & 1], 0));
-  if (used != own) { HIPCHK(hipEventRecord(b->ev_ext, own)); HIPCHK(hipStreamWaitEvent(used, b->ev_ext, 0)); }
-  *used_out = used;
-  return 0;
-}
-static int snap_leave(lm_batch* b, hipStream_t used, int sync) {
-  HIPCHK(hipGetLastError());
-  if (used != b->stream) { HIPCHK(hipEventRecord(b->ev_ext, used)); HIPCHK(hipStreamWaitEvent(b->stream, b->ev_ext, 0)); }
-  if (sync) HIPCHK(hipStreamSynchronize(used));
-  return 0;
-}
-
 extern "C" {
 
 int lm_snapshot_create(lm_batch* b, int flags, lm_snapshot** out) {
@@ -1379,12 +1369,15 @@ int lm_snapshot_save(lm_batch* b, lm_snapshot* s, void* stream, int sync) {
   HIPCHK(hipSetDevice(b->m->device));
   lms::Table t;
   if (!snap_table(b, s->flags, &t) || t.bytes != s->bytes) return fail("lm_snapshot_save: the snapshot's layout does not match the batch");
-  hipStream_t used;
-  if (snap_enter(b, stream, &used)) return 1;
+  StreamScope scope(b, stream);
+  if (scope.enter()) return 1;
   (void)hipGetLastError();
-  lms::launch_copy(t, s->data, nullptr, 0, used);
+  lms::launch_copy(t, s->data, nullptr, 0, scope.used);
   s->step_index = b->step_index; s->saved = true;
-  return snap_leave(b, used, sync);
+  HIPCHK(hipGetLastError());
+  if (scope.leave()) return 1;
+  if (sync) HIPCHK(hipStreamSynchronize(scope.used));
+  return 0;
 }
 
 int lm_snapshot_restore(lm_batch* b, const lm_snapshot* s, const int32_t* d_src, void* stream, int sync) {
@@ -1394,12 +1387,15 @@ int lm_snapshot_restore(lm_batch* b, const lm_snapshot* s, const int32_t* d_src,
   HIPCHK(hipSetDevice(b->m->device));
   lms::Table t;
   if (!snap_table(b, s->flags, &t) || t.bytes != s->bytes) return fail("lm_snapshot_restore: the snapshot's layout does not match the batch");
-  hipStream_t used;
-  if (snap_enter(b, stream, &used)) return 1;
+  StreamScope scope(b, stream);
+  if (scope.enter()) return 1;
   (void)hipGetLastError();
-  lms::launch_copy(t, s->data, d_src, 1, used);
+  lms::launch_copy(t, s->data, d_src, 1, scope.used);
   if (!d_src) b->step_index = s->step_index;      // every environment is back at the save: so is the count that keys the random actions
-  return snap_leave(b, used, sync);
+  HIPCHK(hipGetLastError());
+  if (scope.leave()) return 1;
+  if (sync) HIPCHK(hipStreamSynchronize(scope.used));
+  return 0;
 }
 
 int lm_snapshot_export(lm_batch* b, const lm_snapshot* s, void* host, long long n) {
@@ -1412,10 +1408,10 @@ int lm_snapshot_export(lm_batch* b, const lm_snapshot* s, void* host, long long 
   h.magic = kSnapMagic; h.version = kSnapVersion; h.flags = s->flags; h.step_index = s->step_index; h.bytes = s->bytes;
   for (int i = 0; i < 10; i++) h.sig[i] = s->sig[i];
   memcpy(host, &h, sizeof(h));
-  hipStream_t used;
-  if (snap_enter(b, nullptr, &used)) return 1;
-  HIPCHK(hipMemcpyAsync(static_cast<unsigned char*>(host) + sizeof(h), s->data, (size_t)s->bytes, hipMemcpyDeviceToHost, used));
-  HIPCHK(hipStreamSynchronize(used));
+  StreamScope scope(b, nullptr);
+  if (scope.enter()) return 1;
+  HIPCHK(hipMemcpyAsync(static_cast<unsigned char*>(host) + sizeof(h), s->data, (size_t)s->bytes, hipMemcpyDeviceToHost, scope.used));
+  HIPCHK(hipStreamSynchronize(scope.used));
   return 0;
 }
 
@@ -1431,10 +1427,10 @@ int lm_snapshot_import(lm_batch* b, lm_snapshot* s, const void* host, long long 
   if (h.bytes != s->bytes) return fail("lm_snapshot_import: the blob's payload is not of this snapshot's size");
   if (n < (long long)sizeof(h) + h.bytes) return fail("lm_snapshot_import: the blob is cut short");
   HIPCHK(hipSetDevice(b->m->device));
-  hipStream_t used;
-  if (snap_enter(b, nullptr, &used)) return 1;
-  HIPCHK(hipMemcpyAsync(s->data, static_cast<const unsigned char*>(host) + sizeof(h), (size_t)s->bytes, hipMemcpyHostToDevice, used));
-  HIPCHK(hipStreamSynchronize(used));
+  StreamScope scope(b, nullptr);
+  if (scope.enter()) return 1;
+  HIPCHK(hipMemcpyAsync(s->data, static_cast<const unsigned char*>(host) + sizeof(h), (size_t)s->bytes, hipMemcpyHostToDevice, scope.used));
+  HIPCHK(hipStreamSynchronize(scope.used));
   s->step_index = h.step_index; s->saved = true;
   return 0;
 }

@@ -378,3 +378,68 @@ def test_step_chunk_refusals_give_their_reason():
     assert env._blocks
     with pytest.raises(NotImplementedError, match="several models"):
         env.step_chunk(np.zeros((2, 8, len(env._action_indices))))
+
+
+# ---- 10. a caller's stream with nothing waiting on the host; a refused call
+SIDE_N, SIDE_STEPS = 5, 6      # one full workgroup and one of a single environment; step_device + a tape of 4 (launches of 3 and 1) + step_device
+SIDE_CASES = [("UnitreeA1.simple", None), ("HumanoidTorque.run", 2)]
+
+
+def _six_steps(b, acts, stream, sync):
+    """step_device, rollout_tape of 4 with 3 steps per launch, step_device — then get_state(), which runs on the library's stream."""
+    torch, dev = _torch()
+    n = b.n
+    d_a = torch.from_numpy(np.array(acts)).to(dev)
+    obs = torch.full((SIDE_STEPS, n, b.nobs), OBS_FILL, dtype=torch.float32, device=dev)
+    rew = torch.full((SIDE_STEPS, n), OBS_FILL, dtype=torch.float32, device=dev)
+    done = torch.full((SIDE_STEPS, n), DONE_FILL, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize(dev)
+    kw = dict(stream=stream, sync=sync)
+    b.step_device(action=d_a[0], obs=obs[0], reward=rew[0], done=done[0], **kw)
+    b.rollout_tape(d_a[1:5], obs=obs[1:5], reward=rew[1:5], done=done[1:5], steps_per_launch=3, **kw)
+    b.step_device(action=d_a[5], obs=obs[5], reward=rew[5], done=done[5], **kw)
+    state = b.get_state()                     # no host wait in front of it: the library orders its stream behind the caller's
+    torch.cuda.synchronize(dev)
+    return dict(state=state, obs=obs.cpu().numpy(), reward=rew.cpu().numpy(), done=done.cpu().numpy())
+
+
+@pytest.mark.parametrize("task,replay", SIDE_CASES)
+def test_calls_on_a_side_stream_without_host_waits(task, replay):
+    """Six control steps queued on a torch side stream (not the current one) with sync=False, then get_state() on the library's
+    stream: state and every recorded row are bitwise those of a twin that ran the same six steps synchronously on the library's
+    stream. The quadruped: no replay pass. HumanoidTorque with set_replay(2): every control step goes through the replay kernel —
+    its pollers run on the batch's second stream, and each launch is ordered behind the previous one's drain pass."""
+    torch, dev = _torch()
+    acts = _tape_of(task, SIDE_N, 1.0, steps=SIDE_STEPS)
+    twin = _six_steps(_batch(task, SIDE_N, replay=replay), acts, None, True)
+    side = torch.cuda.Stream(device=dev)
+    assert side.cuda_stream != torch.cuda.current_stream(dev).cuda_stream
+    out = _six_steps(_batch(task, SIDE_N, replay=replay), acts, side.cuda_stream, False)
+    for k in ("obs", "reward", "done"):
+        _same(out[k], twin[k], k + " rows")
+    _same(out["state"][0], twin["state"][0], "final qpos")
+    _same(out["state"][1], twin["state"][1], "final qvel")
+    assert not (twin["obs"] == OBS_FILL).all(2).any() and not (twin["done"] == DONE_FILL).any()      # every row was written
+
+
+def test_a_refused_forward_debug_changes_nothing():
+    """forward_debug at 16 environments per workgroup is refused on the host with its LDS byte counts (nothing is launched): the
+    state stays, and so does the count of control steps that keys the random policy — a random-action rollout afterwards leaves
+    the state of a twin batch that was never refused."""
+    from loco_mujoco_amd.backend import BackendError
+    task = "HumanoidTorque.run"
+    a, twin = _batch(task, SIDE_N, replay=2), _batch(task, SIDE_N, replay=2)
+    q0, v0 = a.get_state()
+    a.set_layout(16)
+    with pytest.raises(BackendError, match="LDS") as err:
+        a.forward_debug(np.zeros((SIDE_N, a.nu)))
+    assert "16 environments per workgroup" in str(err.value) and "forward" in str(err.value), str(err.value)
+    q, v = a.get_state()
+    _same(q, q0, "qpos after the refusal")
+    _same(v, v0, "qvel after the refusal")
+    a.set_layout(4)
+    for b in (a, twin):
+        b.rollout(3, action_mode=1, seed=7)
+    _same(a.get_state()[0], twin.get_state()[0], "qpos after the rollout")
+    _same(a.get_state()[1], twin.get_state()[1], "qvel after the rollout")
+    assert not np.array_equal(a.get_state()[0], q0)
