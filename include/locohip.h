@@ -106,7 +106,9 @@ const char* lm_last_error(void);
 
 /* chain_model: float64 array laid out as in lm_layout.h (header H_* + constant table), produced by the
    host-side mini-compiler + lowering (loco_mujoco_amd/mjcf.py, lowering.py) from the MJCF model and the
-   task description (observation/action spec, termination bounds, reward). */
+   task description (observation/action spec, termination bounds, reward). Refused, with the reason, where no kernel
+   is compiled for the model: six- and seven-link chains outside their families, and a muscle model that no muscle
+   family fits (the generic kernels that serve other cones and integrators have no muscles). */
 int lm_model_create(const double* chain_model, size_t n, int device, lm_model** out);
 void lm_model_destroy(lm_model* m);
 int lm_model_dims(const lm_model* m, lm_dims* out);

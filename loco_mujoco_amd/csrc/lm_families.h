@@ -67,7 +67,8 @@ constexpr Family family(int id) {
 // Which kernel family serves a model: the quadruped family gets a specialised step kernel <3 links, 6 slots, Euler, elliptic,
 // self-collisions>; the humanoid families (five- and six-link chains) are compiled for condim-3 pyramids only (all_pyr3, checked when
 // the model is created): the elliptic code compiles out and the contact slots are compact. Everything else: generic kernels, cone read
-// at run time, plain layout only. -1: no kernel is compiled for the model.
+// at run time, plain layout only — and no muscles: a muscle model that no muscle family fits has no kernel. -1: no kernel is compiled
+// for the model (lm_model_create refuses it with no_family_reason).
 struct ModelFacts { int max_links, max_contacts, integrator, cone, na, npair; bool all_pyr3, root_xyz; };
 constexpr int pick_family(const ModelFacts& m, bool generic_probe /* A/B: run-time cone for the humanoids */) {
   const bool big = m.max_links > 3, six = m.max_links > 5, rk4 = m.integrator == LM_INT_RK4, few = m.max_contacts <= 4;
@@ -76,14 +77,23 @@ constexpr int pick_family(const ModelFacts& m, bool generic_probe /* A/B: run-ti
   if (m.max_links > 6) return (rk4 && m.na == 0 && pyr3) ? 11 : -1;
   if (six) return (!rk4 && m.na == 0 && pyr3) ? 7 : -1;      // (with or without self-collision tables: its regular kernels detect, its replay kernel collides)
   // five-link humanoids whose lowering carries self-collision tables (bone hulls, link meshes, cylinders): the pair families
-  if (big && m.npair > 0 && pyr3) return rk4 ? (m.na == 0 ? 8 : LM_GENERIC_FAMILY) : (m.na == 0 ? 9 : 10);
+  if (big && m.npair > 0 && pyr3) return rk4 ? (m.na == 0 ? 8 : -1) : (m.na == 0 ? 9 : 10);
   // (the quadruped family's Hessian takes the root's translation columns as unit rows: lm_core.h ROOT_XYZ; another root -> generic kernels)
   if (!big && !rk4 && m.na == 0 && m.cone == LM_CONE_ELLIPTIC && m.root_xyz) return 0;
   if (big && rk4 && m.na == 0 && pyr3) return 2;
   if (big && !rk4 && m.na == 0 && pyr3) return 4;
   if (big && !rk4 && m.na > 0 && few && pyr3) return 5;
-  return LM_GENERIC_FAMILY;
+  return m.na > 0 ? -1 : LM_GENERIC_FAMILY;      // (the generic kernels are compiled without muscles: NM = 0 would step the robot with its muscles slack)
 }
+// why pick_family found no kernel for the model
+constexpr const char* no_family_reason(const ModelFacts& m) {
+  return m.max_links > 5 ? "no kernel is compiled for this model: chains of six links are compiled for Euler, of seven links for RK4 — condim-3 pyramids, no muscles only"
+                         : "no kernel is compiled for this model: muscle models need five-link chains, the Euler integrator and condim-3 contacts under pyramidal cones "
+                           "(the generic kernels that serve other cones and integrators have no muscles)";
+}
+// the instance of the generic family that serves a model (lm_family.hip): links and contact slots per chain by the longest chain, the
+// integrator by the part; the cone is read at run time, no muscles, no pair pass, plain layout only
+constexpr Family generic_instance(int max_links, bool rk4) { return max_links > 3 ? Family{true, 5, 8, rk4, -1, 0, 0, 0} : Family{true, 3, 4, rk4, -1, 0, 0, 0}; }
 
 // ---- kernel kinds of one family (picked by the host, lm_kernels.hip::launch_variant)
 enum { LMK_FWD = 0, LMK_REP4, LMK_REP1, LMK_DR_REP4, LMK_DR_REP1, LMK_FUSED, LMK_FUSED_DR, LMK_DRV_REP4, LMK_DRV_REP1, LMK_FUSED_DRV,

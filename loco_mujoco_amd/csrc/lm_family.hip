@@ -21,14 +21,15 @@ bool LM_CAT(launch_f, LM_FAMILY, p, LM_PART)(const LaunchCtx& L0, const KArgs& a
   L.stat_bytes = static_lds_bytes(0);      // (no muscles)
   const dim3 grid((L.N + L.epb - 1) / L.epb), block(4 * L.epb);
   const size_t groups = (block.x + 15) / 16;
-  const bool big = a.T.max_links > 3;
   constexpr bool RK = LM_PART == 1;
+  constexpr Family S = generic_instance(3, RK), B = generic_instance(5, RK);      // (lm_families.h: chains of up to three links | of up to five)
+  const bool big = generic_instance(a.T.max_links, RK).MC == B.MC;
   if (kind == LMK_FWD) {
-    if (!big) launch_one(step_kernel<3, 4, RK, true, -1>, grid, block, (size_t)lm::LaneMem<3, 4>::kGroup * groups, L, a);
-    else launch_one(step_kernel<5, 8, RK, true, -1>, grid, block, (size_t)lm::LaneMem<5, 8>::kGroup * groups, L, a);
+    if (!big) launch_one(step_kernel<S.MC, S.NS, RK, true, S.CONE>, grid, block, (size_t)lm::LaneMem<S.MC, S.NS>::kGroup * groups, L, a);
+    else launch_one(step_kernel<B.MC, B.NS, RK, true, B.CONE>, grid, block, (size_t)lm::LaneMem<B.MC, B.NS>::kGroup * groups, L, a);
   } else if (kind == LMK_REP1) {
-    if (!big) launch_term(step_kernel<3, 4, RK, false, -1>, step_kernel<3, 4, RK, false, -1, 0, 0, 1, false, 0, true>, grid, block, (size_t)lm::LaneMem<3, 4>::kGroup * groups, L, a);
-    else launch_term(step_kernel<5, 8, RK, false, -1>, step_kernel<5, 8, RK, false, -1, 0, 0, 1, false, 0, true>, grid, block, (size_t)lm::LaneMem<5, 8>::kGroup * groups, L, a);
+    if (!big) launch_term(step_kernel<S.MC, S.NS, RK, false, S.CONE>, step_kernel<S.MC, S.NS, RK, false, S.CONE, 0, 0, 1, false, 0, true>, grid, block, (size_t)lm::LaneMem<S.MC, S.NS>::kGroup * groups, L, a);
+    else launch_term(step_kernel<B.MC, B.NS, RK, false, B.CONE>, step_kernel<B.MC, B.NS, RK, false, B.CONE, 0, 0, 1, false, 0, true>, grid, block, (size_t)lm::LaneMem<B.MC, B.NS>::kGroup * groups, L, a);
   } else return false;
   return true;
 #endif

@@ -177,7 +177,7 @@ static std::string layout_refusal(const lm_batch* b, int epb, bool fwd) {
 template <bool FWD>
 static void launch_variant(lm_batch* b, const KArgs& a, hipStream_t stream) {
   const int fam = b->m->family;
-  if (fam < 0) { g_launch_err = "chains of six links are compiled for Euler, of seven links for RK4 — condim-3 pyramids, no muscles only"; return; }
+  if (fam < 0) { g_launch_err = "no kernel is compiled for this model"; return; }      // (lm_model_create refuses such a model: not reached)
   const LaunchCtx L = {stream, b->n_active, b->epb, b->m->lds_limit, &g_launch_err, nullptr, 0};
   if (b->n_active <= 0) return;            // an empty active list: nothing to run
   if (b->lds_ok[FWD] != b->epb) {          // (lm_batch_set_layout refuses such a layout; a model's default layout and the forward kernel are checked here, once)
@@ -186,7 +186,6 @@ static void launch_variant(lm_batch* b, const KArgs& a, hipStream_t stream) {
     b->lds_ok[FWD] = b->epb;
   }
   if (!traits(b).specialised()) {
-    if (b->m->T.na > 0) { g_launch_err = "muscle models need the <5 links, <=4 contacts per chain, Euler> family"; return; }
     if (b->dofprm) { g_launch_err = "per-environment joint parameters are not compiled for this model family"; return; }
     kFamilyTable[fam][b->m->P.integrator == LM_INT_RK4 ? 1 : 0](L, a, FWD ? lmk::LMK_FWD : lmk::LMK_REP1);      // (its parts: Euler | RK4)
     return;
@@ -291,7 +290,9 @@ int lm_model_create(const double* cmod, size_t n, int device, lm_model** out) {
   if (LM_PROBE_ENV("LM_NO_PAIRS")) for (int c = 0; c < LM_NCHAIN; c++) pm.cm[LM_CM_CHAINS + LM_C_NLPAIR * LM_NCHAIN + c] = 0.0f;      // A/B: self-collision broad phase off
   m->T = pm.T; m->root_limited = pm.root_limited; m->n_gpt_floats = pm.n_gpt_floats; m->nominal = std::move(pm.nominal);
   static const bool generic = LM_PROBE_ENV("LM_GENERIC_KERNELS") != nullptr;      // A/B: run-time cone for the humanoids
-  m->family = lmk::pick_family({pm.T.max_links, pm.T.max_contacts, pm.integrator, pm.cone, pm.T.na, pm.T.npair, pm.T.all_pyr3 != 0, pm.root_xyz}, generic);
+  const lmk::ModelFacts facts = {pm.T.max_links, pm.T.max_contacts, pm.integrator, pm.cone, pm.T.na, pm.T.npair, pm.T.all_pyr3 != 0, pm.root_xyz};
+  m->family = lmk::pick_family(facts, generic);
+  if (m->family < 0) return fail(lmk::no_family_reason(facts));      // refused HERE, not at the first launch
   if (upload(pm.cm, &m->d_cm) || upload(pm.gt, &m->d_gt) || (!pm.mt.empty() && upload(pm.mt, &m->d_mt)) || upload(pm.gpt, &m->d_gpt) ||
       upload(pm.meshv, &m->d_meshv) || upload(pm.meshn, &m->d_meshn) || upload(pm.bpt, &m->d_bpt) || upload(pm.meshadj, &m->d_meshadj)) return 1;
   lm::Params& P = m->P;

@@ -16,6 +16,7 @@
 #define LM_OPAQUE_ZERO() 0
 #define LM_POW01(x, p) exp2f((p) * log2f(x))
 #include "../../loco_mujoco_amd/csrc/lm_core.h"
+#include "../../loco_mujoco_amd/csrc/lm_families.h"
 
 #ifndef EMU_SIX_PAIRS
 #define EMU_SIX_PAIRS 1
@@ -135,11 +136,12 @@ const double* g_dofprm = nullptr;
 const float* g_vrec = nullptr; const float* g_vgt = nullptr; const float* g_vgpt = nullptr;
 }  // namespace
 
-// EMU_PYRAMID_ONLY compiles the humanoid families like the library does (condim-3 pyramids only, elliptic code out)
+// EMU_PYRAMID_ONLY compiles every family for the cone the library compiles it for (lm_families.h: the humanoid families condim-3
+// pyramids only, the elliptic code out; the generic family reads the header's cone at run time); without it the humanoids read it too
 #ifdef EMU_PYRAMID_ONLY
-template <int MC> constexpr int kEmuCone = (MC >= 5) ? 0 : -1;
+constexpr int emu_cone(const lmk::Family& f) { return f.CONE; }
 #else
-template <int MC> constexpr int kEmuCone = -1;
+constexpr int emu_cone(const lmk::Family& f) { return f.MC <= 3 ? f.CONE : -1; }
 #endif
 
 // chain_model: float64 [HEADER + CM]; state arrays [n][nv] double in/out; ctrl [n][nu] (already un-normalised)
@@ -148,7 +150,7 @@ template <int MC> constexpr int kEmuCone = -1;
 // leave / only: the device's speculate / replay protocol (lm_step.h). With `leave` a control step that runs out of contact slots or
 // list space, or meets a convex pair without having the collider, stores NOTHING and sets leave[e]; with `only` the environments
 // whose flag is 0 are skipped (the replay pass of the big instantiation over the flagged ones).
-template <int MC, int NS, bool RK4, int NM = 0, int PM = 0>
+template <int MC, int NS, bool RK4, int NM, int PM, int CONE>
 static int emu_run_t(const double* chain_model, int n, double* qpos, double* qvel, double* warm, const double* action,
                      int nsub, int debug_env, float* dbgM, float* dbg5, int* counters, double* act = nullptr,
                      int* leave = nullptr, const int* only = nullptr) {
@@ -254,7 +256,7 @@ static int emu_run_t(const double* chain_model, int n, double* qpos, double* qve
         }
       }
       lm::Counters cnt = {};
-      using LMm = lm::LaneMemFor<MC, NS, NM, PAIRS, kEmuCone<MC>>;
+      using LMm = lm::LaneMemFor<MC, NS, NM, PAIRS, CONE>;
       float lmem[LMm::kSize];
       // rep = 1: lane memory starts uninitialised (MemorySanitizer sees reads of never-written words); replicated: every
       // private copy and the snapshot start as the same quiet NaN, so such a read poisons the result instead
@@ -279,7 +281,7 @@ static int emu_run_t(const double* chain_model, int n, double* qpos, double* qve
       lm::Debug dbg = {dbgM, dbg5, dbg5 + nv, dbg5 + 2 * nv, dbg5 + 3 * nv, dbg5 + 4 * nv};
       float pair_slack[3] = {0.0f, 0.0f, 0.0f};
       for (int s = 0; s < nsub; s++)
-        lm::substep<QuadThreads, MC, NS, RK4, (PAIRS && MC <= 3) ? 1 : kEmuCone<MC>, NM, kEmuDR, PM>(cm.data(), c, P, qr, vr, qc, vc, war, wac, actr, actc, lmem, 1, cnt,
+        lm::substep<QuadThreads, MC, NS, RK4, CONE, NM, kEmuDR, PM>(cm.data(), c, P, qr, vr, qc, vc, war, wac, actr, actc, lmem, 1, cnt,
                                                       (e == debug_env && s == 0 && dbgM && t_rep == 0) ? &dbg : nullptr, mt.data(), &dofp, false, pair_slack);
       QuadThreads::fence();          // like the kernel before it stores: the activations were updated by their owner replicas
       static int acc[64][9];
@@ -334,32 +336,64 @@ static int emu_run_t(const double* chain_model, int n, double* qpos, double* qve
 extern "C" void emu_set_dof_params(const double* p) { g_dofprm = p; }
 extern "C" void emu_set_model_variant(const float* rec, const float* gt, const float* gpt) { g_vrec = rec; g_vgt = gt; g_vgpt = gpt; }
 
-// same family selection as the library's launch_variant(); BIGK = the family's replay instantiation (lm_step.h launch_family: 128
-// slots per chain, the convex collider)
+// The library's own selection (lm_families.h): pick_family over the facts lm_model_parse.h derives from the blob, then the family's row —
+// links, slots, integrator, compiled-in cone, muscles, pair pass — or, for the generic family, generic_instance. BIGK = the family's
+// replay instantiation (lm_step.h launch_family: 128 slots per chain, the convex collider); the generic family has none.
+static lmk::ModelFacts emu_facts(const double* H) {
+  bool pyr3 = (int)H[LM_H_CONE] == LM_CONE_PYRAMIDAL, root_xyz = (float)H[LM_HEADER_SIZE + LM_R_NDOF] == 6.0f;
+  for (int c = 0; c < LM_NCHAIN && pyr3; c++) {
+    const int ng = (int)H[LM_HEADER_SIZE + LM_CM_CHAINS + LM_C_NGEOMS * LM_NCHAIN + c];
+    for (int g = 0; g < ng; g++) if ((int)H[LM_HEADER_SIZE + LM_CM_SIZE + (g * LM_G_SIZE + LM_G_DIM) * LM_NCHAIN + c] != 3) pyr3 = false;
+  }
+  const double* cm = H + LM_HEADER_SIZE;
+  for (int i = 0; i < 9; i++) if ((float)cm[LM_R_R0 + i] != ((i % 4 == 0) ? 1.0f : 0.0f)) root_xyz = false;
+  for (int i = 0; i < 3; i++) {
+    const double* d = cm + LM_R_DOFS + i * LM_D_SIZE;
+    if ((float)d[LM_D_TYPE] != 0.0f) root_xyz = false;
+    for (int k = 0; k < 3; k++) if ((float)d[LM_D_AX + k] != ((k == i) ? 1.0f : 0.0f)) root_xyz = false;
+  }
+  return {(int)H[LM_H_MAXLINKS], (int)H[LM_H_MAXCONTACTS], (int)H[LM_H_INTEGRATOR], (int)H[LM_H_CONE], (int)H[LM_H_NMUSCLE], (int)H[LM_H_NGPAIR], pyr3, root_xyz};
+}
+// what the regular (BIGK: the replay) instantiation of family `id` is for this blob, as the library launches it; present = false: none
+static lmk::Family emu_instance_of(const double* H, int id, bool bigk) {
+  lmk::Family f = lmk::family(id);
+  if (id == LM_GENERIC_FAMILY) return bigk ? lmk::Family{} : lmk::generic_instance((int)H[LM_H_MAXLINKS], (int)H[LM_H_INTEGRATOR] == LM_INT_RK4);
+  if (!f.present) return f;
+  if (bigk) { f.NS = 128; f.PM = f.PM != 0 ? 1 : 0; }
+  else if (id == 7) f.PM = EMU_SIX_PAIRS;      // (lm_families.h LM_SIX_PAIRS: 1 the whole pair pass, 3 detection only)
+  return f;
+}
+// [family id, present, MC, NS, RK4, CONE, NM, PM] of the regular (bigk = 0) or replay instantiation this emulator runs for the blob
+extern "C" void emu_instance(const double* chain_model, int bigk, int* out) {
+  const int id = lmk::pick_family(emu_facts(chain_model), false);
+  const lmk::Family f = emu_instance_of(chain_model, id, bigk != 0);
+  const int v[8] = {id, f.present, f.MC, f.NS, f.RK4, f.present ? emu_cone(f) : 0, f.NM, f.PM};
+  for (int i = 0; i < 8; i++) out[i] = v[i];
+}
+
 template <bool BIGK>
 static int emu_dispatch(const double* chain_model, int n, double* qpos, double* qvel, double* warm, const double* action,
                         int nsub, int debug_env, float* dbgM, float* dbg5, int* counters, double* act, int* leave, const int* only) {
-  constexpr int N4 = BIGK ? 128 : 4, N8 = BIGK ? 128 : 8, N6 = BIGK ? 128 : 6;
 #define EMU_ARGS chain_model, n, qpos, qvel, warm, action, nsub, debug_env, dbgM, dbg5, counters
-  const bool rk4 = (int)chain_model[LM_H_INTEGRATOR] == LM_INT_RK4;
-  const bool big = (int)chain_model[LM_H_MAXLINKS] > 3, few = (int)chain_model[LM_H_MAXCONTACTS] <= 4;
-  if ((int)chain_model[LM_H_MAXLINKS] > 5)
-    return (!rk4 && (int)chain_model[LM_H_NMUSCLE] == 0) ? emu_run_t<6, N8, false, 0, BIGK ? 1 : EMU_SIX_PAIRS>(EMU_ARGS, nullptr, leave, only) : -1;      // (lm_family.hip LM_SIX_PAIRS: 1 the whole pair pass, 3 detection only | the replay kernel's pair pass)
-  // the five-link humanoids with self-collision tables (bone hulls, UnitreeH1's cylinders and meshes): the pair families, 8 slots
-  if ((int)chain_model[LM_H_NGPAIR] > 0 && big) {
-    if ((int)chain_model[LM_H_NMUSCLE] > 0) return (act && !rk4) ? emu_run_t<5, N8, false, LM_MAXMUS, 1>(EMU_ARGS, act, leave, only) : -1;
-    return rk4 ? emu_run_t<5, N8, true, 0, 1>(EMU_ARGS, nullptr, leave, only) : emu_run_t<5, N8, false, 0, 1>(EMU_ARGS, nullptr, leave, only);
+  const int id = lmk::pick_family(emu_facts(chain_model), false);
+  const bool rk4 = (int)chain_model[LM_H_INTEGRATOR] == LM_INT_RK4, big = (int)chain_model[LM_H_MAXLINKS] > 3;
+  switch (id) {
+#define LM_X(ID, ...)                                                                                                               \
+    case ID: if constexpr (ID != LM_GENERIC_FAMILY) {                                                                                 \
+      constexpr lmk::Family F = lmk::family(ID);                                                                                      \
+      constexpr int PM = BIGK ? (F.PM != 0 ? 1 : 0) : (ID == 7 ? EMU_SIX_PAIRS : F.PM);                                               \
+      if (F.NM > 0 && !act) return -1;                                                                                                \
+      return emu_run_t<F.MC, BIGK ? 128 : F.NS, F.RK4, F.NM, PM, emu_cone(F)>(EMU_ARGS, F.NM > 0 ? act : nullptr, leave, only);       \
+    } break;
+    LM_FAMILY_LIST(LM_X)
+#undef LM_X
   }
-  if ((int)chain_model[LM_H_NMUSCLE] > 0)
-    return (act && big && !rk4 && few) ? emu_run_t<5, N4, false, LM_MAXMUS>(EMU_ARGS, act, leave, only) : -1;
-  // the quadruped (LM_A1_PAIRS = 2 in lm_family.hip: the regular kernels leave the convex collider to the replay kernel)
-  if (!big && !rk4 && (int)chain_model[LM_H_CONE] == LM_CONE_ELLIPTIC) return emu_run_t<3, N6, false, 0, BIGK ? 1 : 2>(EMU_ARGS, nullptr, leave, only);
-  if (!big && !rk4) return emu_run_t<3, 5, false>(EMU_ARGS, nullptr, BIGK ? nullptr : leave, only);          // (generic family: no replay kernel)
-  if (!big && rk4) return emu_run_t<3, 4, true>(EMU_ARGS, nullptr, BIGK ? nullptr : leave, only);
-  if (!rk4 && few) return emu_run_t<5, N4, false>(EMU_ARGS, nullptr, leave, only);
-  if (!rk4) return emu_run_t<5, N8, false>(EMU_ARGS, nullptr, leave, only);
-  if (few) return emu_run_t<5, N4, true>(EMU_ARGS, nullptr, leave, only);
-  return emu_run_t<5, N8, true>(EMU_ARGS, nullptr, leave, only);
+  if (id != LM_GENERIC_FAMILY) return -1;      // no kernel is compiled for the model
+  // the generic family (lm_family.hip): no replay kernel — a control step beyond its slots drops contacts and counts them
+  constexpr lmk::Family S = lmk::generic_instance(3, false), B = lmk::generic_instance(5, false);
+  int* lv = BIGK ? nullptr : leave;
+  if (!big) return rk4 ? emu_run_t<S.MC, S.NS, true, 0, 0, S.CONE>(EMU_ARGS, nullptr, lv, only) : emu_run_t<S.MC, S.NS, false, 0, 0, S.CONE>(EMU_ARGS, nullptr, lv, only);
+  return rk4 ? emu_run_t<B.MC, B.NS, true, 0, 0, B.CONE>(EMU_ARGS, nullptr, lv, only) : emu_run_t<B.MC, B.NS, false, 0, 0, B.CONE>(EMU_ARGS, nullptr, lv, only);
 #undef EMU_ARGS
 }
 

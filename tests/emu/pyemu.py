@@ -19,7 +19,7 @@ def build(ls_points=1, dr=False, rep=1):
     replicated small-batch layout (evaluated by one lane here); dr: 1 = the per-environment joint-parameter code path, 2 = with
     model variants (the kernels' DR template level)."""
     srcs = [os.path.join(_HERE, "emu.cpp"), os.path.join(_HERE, "../../loco_mujoco_amd/csrc/lm_core.h"),
-            os.path.join(_HERE, "../../include/lm_layout.h")]
+            os.path.join(_HERE, "../../loco_mujoco_amd/csrc/lm_families.h"), os.path.join(_HERE, "../../include/lm_layout.h")]
 
     def stale(lib):
         return not os.path.exists(lib) or any(os.path.getmtime(s) > os.path.getmtime(lib) for s in srcs)

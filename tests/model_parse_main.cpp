@@ -8,6 +8,9 @@
 //   model_parse pokes FILE...   the refusals that guard reads outside the buffer: a chain's geom count and link count at the largest value
 //                               whose reads stay inside (must not be refused for it, and no sanitizer report) and one more (refused);
 //                               an optional table's count / offset negative, not a number, huge, beyond the blob (refused)
+//   model_parse instances FILE...   one line per blob: the family and the instantiation of its regular kernel — links and contact slots per chain,
+//                               integrator, compiled-in cone (-1: read at run time), muscles per chain, pair pass (lm_families.h family(),
+//                               generic_instance) — that the library launches for it; family -1: the refusal's reason
 //   model_parse kinds           one line per family id: which of the LMK_* kinds the family table says it has
 #include <cmath>
 #include <cstdio>
@@ -71,6 +74,22 @@ int parse(const char* path) {
                      m.n_gpt_floats == (int)(ngp * LM_GPAIR_SIZE) && m.meshv.size() == 4 * nmv + 4 && m.meshn.size() == nmn + 1 && m.meshn.back() == -1.0f &&
                      m.bpt.size() == nbp * LM_BP_SIZE + 1 && m.meshadj.size() == 4 * nadj + 64 && m.nominal.size() == (size_t)3 * m.T.nv;
   if (!sizes) { printf("%s: table sizes\n", stem(path).c_str()); return 1; }
+  return 0;
+}
+
+int instance(const char* path) {
+  std::vector<double> all;
+  if (!load(path, &all)) { printf("%s: cannot read\n", path); return 1; }
+  lmp::ParsedModel m;
+  std::string why;
+  if (!lmp::parse_model(exact(all, all.size()).get(), all.size(), &m, &why)) { printf("%s refused: %s\n", stem(path).c_str(), why.c_str()); return 1; }
+  const int id = family_of(m);
+  if (id < 0) {
+    printf("%s family -1 refused: %s\n", stem(path).c_str(), lmk::no_family_reason({m.T.max_links, m.T.max_contacts, m.integrator, m.cone, m.T.na, m.T.npair, m.T.all_pyr3 != 0, m.root_xyz}));
+    return 0;
+  }
+  const lmk::Family f = id == LM_GENERIC_FAMILY ? lmk::generic_instance(m.T.max_links, m.integrator == LM_INT_RK4) : lmk::family(id);
+  printf("%s family %d present %d MC %d NS %d RK4 %d CONE %d NM %d PM %d\n", stem(path).c_str(), id, (int)f.present, f.MC, f.NS, (int)f.RK4, f.CONE, f.NM, f.PM);
   return 0;
 }
 
@@ -156,7 +175,7 @@ int main(int argc, char** argv) {
       printf("\n");
     }
   } else {
-    for (int i = 2; i < argc; i++) bad += mode == "cuts" ? cuts(argv[i]) : mode == "pokes" ? pokes(argv[i]) : parse(argv[i]);
+    for (int i = 2; i < argc; i++) bad += mode == "cuts" ? cuts(argv[i]) : mode == "pokes" ? pokes(argv[i]) : mode == "instances" ? instance(argv[i]) : parse(argv[i]);
   }
   if (bad) return 1;
   printf("model parse: ok\n");

@@ -35,6 +35,17 @@ FAMILIES = {
     "UnitreeH1.default": 9, "UnitreeH1.noback": 9,
 }
 EXTRA = {"mesh_feet": 11, "HumanoidMuscle.default.nopairs": 5, "UnitreeA1.torque.rk4": 6, "UnitreeG1.legs.rk4": -1}
+# The models of tests/test_generic_family_gpu.py (generic_family_common.CASES: the compiled model edited before it is lowered), so that
+# none of them drifts into a specialised family unnoticed; and the two such edits that have no kernel: six-link chains under an elliptic
+# cone, and a muscle model under one — the generic kernels are compiled without muscles, so pick_family refuses it.
+EDITED = {"UnitreeA1.torque.pyramidal3": ("UnitreeA1.torque", "_pyramidal_condim3", 6), "Talos.default.elliptic": ("Talos.default", "_elliptic", 6),
+          "Atlas.default.elliptic": ("Atlas.default", "_elliptic", 6), "HumanoidTorque.default.elliptic": ("HumanoidTorque.default", "_elliptic", 6),
+          "UnitreeH1.default.elliptic": ("UnitreeH1.default", "_elliptic", 6), "UnitreeG1.default.elliptic": ("UnitreeG1.default", "_elliptic", -1),
+          "HumanoidMuscle.default.elliptic": ("HumanoidMuscle.default", "_elliptic", -1)}
+EXTRA.update((k, v[2]) for k, v in EDITED.items())
+# the instance <links, slots, RK4> of the generic family that serves each of its blobs (lm_families.h generic_instance)
+GENERIC_INSTANCE = {"UnitreeA1.torque.rk4": (3, 4, 1), "UnitreeA1.torque.pyramidal3": (3, 4, 0), "Talos.default.elliptic": (5, 8, 0), "Atlas.default.elliptic": (5, 8, 1),
+                    "HumanoidTorque.default.elliptic": (5, 8, 1), "UnitreeH1.default.elliptic": (5, 8, 0)}
 # the tasks of tests/test_plain_layout_gpu.py FAMILY and the blob of the same robot here
 SAME_ROBOT = {"UnitreeA1.simple": "UnitreeA1.torque", "Atlas.walk": "Atlas.default", "Talos.walk": "Talos.default", "HumanoidTorque.run": "HumanoidTorque.default",
               "UnitreeH1.run": "UnitreeH1.default", "UnitreeG1.walk": "UnitreeG1.default", G.MESH: "mesh_feet", G.MUSCLE: "HumanoidMuscle.default",
@@ -83,6 +94,11 @@ def parse(tmp_path_factory):
     for src in ("UnitreeA1.torque", "UnitreeG1.legs"):
         blobs[src + ".rk4"] = blobs[src].copy()
         blobs[src + ".rk4"][lowering.H_INTEGRATOR] = 1.0
+    import generic_family_common as GF
+    for name, (src, edit, _) in EDITED.items():
+        m = mjcf.CompiledModel.load(os.path.join(ASSETS, src + ".model.npz"))
+        getattr(GF, edit)(m)
+        blobs[name] = np.ascontiguousarray(lowering.lower(m, _neutral_task(m))[0], dtype=np.float64)
     for name, blob in blobs.items():
         blob.tofile(str(tmp / (name + ".bin")))
 
@@ -94,6 +110,7 @@ def parse(tmp_path_factory):
         assert lines[-1] == "model parse: ok"
         return lines[:-1]
 
+    run.blobs = blobs
     return run
 
 
@@ -109,6 +126,44 @@ def test_family_of_every_shipped_model(parse):
     assert len(FAMILIES) == 35 and sorted(set(want.values())) == [-1, 0, 2, 4, 5, 6, 7, 8, 9, 10, 11]
     for task, fam in G.FAMILY.items():
         assert want[SAME_ROBOT[task]] == fam, task
+
+
+def test_generic_family_serves_each_of_its_models_with_the_stated_instance(parse):
+    """Every blob of family 6: links and contact slots per chain and the integrator of the instance that lm_family.hip launches
+    (generic_instance), cone read at run time, no muscles, no pair pass. The models no kernel is compiled for are refused with a reason
+    that names it — the muscle model because the generic kernels have no muscles."""
+    want = dict(FAMILIES, **EXTRA)
+    generic = sorted(k for k, v in want.items() if v == 6)
+    assert generic == sorted(GENERIC_INSTANCE)
+    for ln in parse("instances", generic):
+        w = ln.split()
+        assert tuple(int(w[i]) for i in (2, 4, 6, 8, 10, 12, 14, 16)) == (6, 1) + GENERIC_INSTANCE[w[0]][:2] + (GENERIC_INSTANCE[w[0]][2], -1, 0, 0), ln
+    assert sorted(set(GENERIC_INSTANCE.values())) == [(3, 4, 0), (3, 4, 1), (5, 8, 0), (5, 8, 1)]          # every instance is reached
+    refused = dict((ln.split()[0], ln.split("refused: ", 1)[1]) for ln in parse("instances", sorted(k for k, v in want.items() if v == -1)))
+    assert sorted(refused) == ["HumanoidMuscle.default.elliptic", "UnitreeG1.default.elliptic", "UnitreeG1.legs.rk4"]
+    assert "have no muscles" in refused["HumanoidMuscle.default.elliptic"] and "muscle models need" in refused["HumanoidMuscle.default.elliptic"]
+    assert all("chains of six links" in refused[k] for k in ("UnitreeG1.default.elliptic", "UnitreeG1.legs.rk4"))
+
+
+def test_emulator_picks_the_librarys_instance_for_every_blob(parse):
+    """tests/emu/emu.cpp chooses through pick_family and family() of lm_families.h, like lm_model_create and the launch code: for every
+    blob here the emulator's regular instantiation is the library's — family, links, slots, integrator, muscles, pair pass, and the
+    compiled-in cone — and a model without a family has none."""
+    from emu import pyemu
+    lib = C.CDLL(pyemu.build())
+    want = dict(FAMILIES, **EXTRA)
+    n = 0
+    for ln in parse("instances", sorted(want)):
+        w = ln.split()
+        out = (C.c_int * 8)()
+        blob = parse.blobs[w[0]]
+        lib.emu_instance(blob.ctypes.data_as(C.c_void_p), 0, out)
+        if want[w[0]] < 0:
+            assert w[2] == "-1" and (out[0], out[1]) == (-1, 0), ln
+        else:
+            assert list(out) == [int(w[i]) for i in (2, 4, 6, 8, 10, 12, 14, 16)], (ln, list(out))
+            n += 1
+    assert n == len(want) - 3
 
 
 def test_derived_task_facts_of_one_model_per_family(parse):

@@ -17,12 +17,12 @@ import pytest
 
 import step_bookkeeping_model as M
 from loco_mujoco_amd import LocoEnv
-from test_terminal_obs_gpu import N_PUSHED, _load, _raw_step, _start_rows, _task
+from test_terminal_obs_gpu import GENERIC, N_PUSHED, _load, _raw_step, _start_rows, _task
 
 pytestmark = pytest.mark.gpu
 
-FAMILIES = ["UnitreeA1.simple", "Atlas.walk", "Talos.walk", "HumanoidTorque.run", "HumanoidMuscle.run", "UnitreeG1.walk"]
-GENERIC = "UnitreeG1.walk"   # the generic kernel family: one layout, no fused kernels
+# (GENERIC: the quadruped under RK4 — the generic kernel family: one layout, no fused kernels, a rollout runs one control step per launch)
+FAMILIES = ["UnitreeA1.simple", "Atlas.walk", "Talos.walk", "HumanoidTorque.run", "HumanoidMuscle.run", "UnitreeG1.walk", GENERIC]
 N = 37                       # nine full workgroups of four environments and a padded one
 OFFSET = 1000                # global_env_offset: the draws are keyed by OFFSET + e
 SEED = 5
@@ -92,7 +92,7 @@ def _wanted_rows(seed_eff):
 # no test launches it. At 8 per workgroup the kernel takes 95 704 B: "plain8")
 _STEP_CASES = ([(t, "step") for t in FAMILIES] + [(t, "replay") for t in ("HumanoidTorque.run", "HumanoidMuscle.run")]
                + [(t, "plain16") for t in FAMILIES if t not in (GENERIC, "HumanoidMuscle.run")] + [("HumanoidMuscle.run", "plain8")]
-               + [(t, "active") for t in FAMILIES if t != "UnitreeA1.simple"])              # (the quadruped's kernels have no active lists)
+               + [(t, "active") for t in FAMILIES if t != "UnitreeA1.simple"])              # (the quadruped family's kernels have no active lists; the generic ones do)
 
 
 @pytest.mark.parametrize("task,mode", _STEP_CASES)

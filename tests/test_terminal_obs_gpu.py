@@ -16,15 +16,19 @@ from loco_mujoco_amd import LocoEnv
 pytestmark = pytest.mark.gpu
 
 H = 3            # horizon of the twin runs: H + 1 control steps
+GENERIC = "UnitreeA1.simple.rk4"      # the quadruped under RK4: no specialised family fits it, the generic kernels serve it (lm_families.h)
 N_PUSHED = 12    # environments started just inside a termination bound with a velocity that crosses it
 
 
 @functools.lru_cache(maxsize=None)
 def _task(task, foot_forces=False):
-    """(env, HipModel, reset table): one lowering per task for the whole module (read-only)."""
+    """(env, HipModel, reset table): one lowering per task for the whole module (read-only). GENERIC: UnitreeA1.simple with the compiled
+    model's integrator set to RK4 in memory."""
     from loco_mujoco_amd.backend import HipModel
     np.random.seed(0)
-    env = LocoEnv.make(task, debug=True, **(dict(use_foot_forces=True) if foot_forces else {}))
+    env = LocoEnv.make(task[:-len(".rk4")] if task == GENERIC else task, debug=True, **(dict(use_foot_forces=True) if foot_forces else {}))
+    if task == GENERIC:
+        env._model.integrator = 1
     return env, HipModel(env._chain_model()), env._reset_table()
 
 
@@ -116,11 +120,12 @@ def _check_twin(env, steps, n, ngrf=0):
 @pytest.mark.parametrize("task,n,kw", [("UnitreeA1.simple", 37, {}), ("HumanoidTorque.run", 64, {}), ("HumanoidMuscle.run", 64, {}),
                                        ("HumanoidTorque.walk", 64, dict(foot_forces=True)),
                                        ("UnitreeA1.simple", 37, dict(replay=2)), ("UnitreeA1.simple", 37, dict(layout=16)),
-                                       ("HumanoidTorque.run", 64, dict(layout=16))])
+                                       ("HumanoidTorque.run", 64, dict(layout=16)), (GENERIC, 37, {})])
 def test_terminal_row_is_the_twin_batchs_observation_bitwise(task, n, kw):
     """At the first step in which A's done byte has bit 1, A's terminal row equals the observation of the twin that did not restart,
     bit for bit: dataset rows (n = 37: a ragged last workgroup) of which twelve leave a termination bound in the first step, the others
-    run into the horizon. With foot forces the terminal row carries this step's mean force, the fresh observation zeros."""
+    run into the horizon. With foot forces the terminal row carries this step's mean force, the fresh observation zeros. GENERIC: the
+    terminal-observation instance of the generic family's kernels (lm_family.hip launch_term)."""
     env, A, steps = _twin_run(task, n, **kw)
     ngrf = env._get_grf_size() if kw.get("foot_forces") else 0
     _check_twin(env, steps, n, ngrf)
