@@ -38,6 +38,8 @@
  *   lm_rollout_tape     <- the same loop over a GIVEN action sequence, `for a in actions: env.step(a)` with no policy decision
  *                          inside (action repeat / frame skip, K-step action chunks, sampling planners, open-loop replay of
  *                          recorded actions), with every step's observation, reward and done byte recorded
+ *   lm_rollout_policy   <- the same loop with a policy inside, `a = policy(obs); obs, r, absorbing, _ = env.step(a)`: a small MLP evaluated
+ *                          on the device at the top of every control step, its actions recorded as a tape
  *   lm_forward_debug    <- mujoco.mj_forward (base.py:362) with intermediate results, for parity tests
  *   lm_snapshot_create / _save / _restore / _export / _import <- copy.copy(data) / mujoco.mj_copyData of every environment's MjData
  *                          (the reference keeps one MjData per environment on the host, base.py:185; it has no call of its own for
@@ -262,8 +264,8 @@ int lm_rollout(lm_batch* b, int n_steps, int action_mode, uint64_t seed, lm_stat
 /* The same rollout with `steps_per_launch` control steps per kernel launch: every environment advances on its own, without
    the device-wide join that ends each single-step launch with its slowest environment. Bitwise the same states,
    observations and statistics as lm_rollout (which is steps_per_launch = 1). It keeps the LAST step's observation, reward and done
-   byte; actions that are known ahead for several steps go through lm_rollout_tape, a policy that decides every step needs
-   lm_step / lm_step_device. */
+   byte; actions that are known ahead for several steps go through lm_rollout_tape, a small MLP policy that decides every step
+   through lm_rollout_policy; any other policy needs lm_step / lm_step_device. */
 int lm_rollout_fused(lm_batch* b, int n_steps, int steps_per_launch, int action_mode, uint64_t seed, lm_stats* stats);
 
 /* ACTION TAPES: n_steps control steps under given actions, `steps_per_launch` of them per kernel launch, every step recorded.
@@ -291,6 +293,47 @@ int lm_rollout_fused(lm_batch* b, int n_steps, int steps_per_launch, int action_
    into *stats (kernel_ms: this call's, by HIP events); with sync = 0 *stats is not written. */
 int lm_rollout_tape(lm_batch* b, int n_steps, int steps_per_launch, const float* d_actions, long long action_step_stride,
                     float* d_obs, float* d_reward, uint8_t* d_done, float* d_term, void* stream, int sync, lm_stats* stats);
+
+/* CLOSED-LOOP POLICY ROLLOUTS: lm_rollout_tape with the actions computed on the device by a small MLP policy, step by step, from the
+   observation the previous step wrote — the reference's `for t in range(K): a = policy(obs); obs, r, absorbing, _ = env.step(a)`
+   (examples/reinforcement_learning: mushroom-rl's Core.learn loop around LocoEnv.step, base.py:344-373) without a host round trip
+   or a torch launch per step. The policy is a plain description, read in place at every step; the library keeps nothing of it:
+     n_layers, sizes      1..3 linear layers; sizes[0] = the model's nobs, sizes[n_layers] = its nu, the widths between 1..256
+     activation           after every layer but the last (the output layer is linear; the actuator's clamp bounds the control as it
+                          does for any tape action): 0 tanh, 1 relu
+     d_params             DEVICE float32, per layer W [out][in] row-major, then b [out] — torch.nn.utils.parameters_to_vector of a
+                          Sequential(Linear, act, Linear, act, Linear)
+     d_log_std            DEVICE float32 [nu], or NULL: the action is the MLP's output (deterministic). Otherwise
+                          a[k] = mean[k] + exp(d_log_std[k]) * z, z ~ N(0, 1) by Box-Muller on the counter-based generator, keyed by
+                          (noise_seed, GLOBAL environment id, the batch's count of control steps at that step, k) under a salt of its
+                          own: neither the uniform actions of lm_rollout nor the restart draws share numbers with it.
+   Every unit accumulates in float32 in one fixed order (bias, then the inputs in index order, fused multiply-adds): an action does not
+   depend on the launch split, the batch size or the environment's place in the batch. */
+typedef struct {
+  int n_layers;            /* 1..3 linear layers */
+  int sizes[4];            /* sizes[0] == nobs, sizes[n_layers] == nu, hidden widths 1..256 (any value, not only multiples of 16) */
+  int activation;          /* after every layer but the last: 0 tanh, 1 relu */
+  const float* d_params;   /* DEVICE, float32, per layer: W [out][in] row-major, then b [out] */
+  const float* d_log_std;  /* DEVICE [nu] or NULL (deterministic) */
+} lm_mlp_policy;
+/*   d_obs0               DEVICE [n_envs][nobs]: the observation the FIRST action is computed from, in the kernel's column order (the
+                          one lm_step_device writes, not lm_set_obs_order's). NULL: the batch's own last-step row — valid after any
+                          step of this batch, NOT after lm_set_state (which leaves that row as it was: pass the reset observation).
+     d_actions            DEVICE [n_steps][n_envs][nu], required: step t's action is written to row t (the raw a, before the actuator's
+                          clamp) and read from there by the step — the recorded tape fed to lm_rollout_tape repeats the rollout bitwise.
+     d_obs, d_reward, d_done, d_term, steps_per_launch, stream, sync, stats
+                          as in lm_rollout_tape (d_obs NULL: the batch's own row; the policy then reads that row).
+   Every argument is checked before the first launch (the sizes against the model's nobs / nu, layer count, widths, null pointers): a
+   refused call launches nothing and leaves the count of control steps where it was. Under an active list the rows of inactive
+   environments are left as they were, the action tape's included.
+   A launch of several control steps evaluates the policy inside the fused step kernel, at the top of every step; a launch of one
+   control step (steps_per_launch = 1, a ragged last launch, and wherever lm_rollout_tape runs one step per launch: layouts of more than
+   4 environments per workgroup, families without replicas, the model compiler) runs a small kernel of its own in front of the ordinary
+   step kernel, on the same stream and without a host wait. Both run the same device function: the action tape is bitwise the same
+   whatever steps_per_launch is. */
+int lm_rollout_policy(lm_batch* b, const lm_mlp_policy* p, int n_steps, int steps_per_launch, uint64_t noise_seed,
+                      const float* d_obs0, float* d_actions, float* d_obs, float* d_reward, uint8_t* d_done,
+                      float* d_term, void* stream, int sync, lm_stats* stats);
 
 /* SNAPSHOTS: the state of every environment of a batch, kept in device memory — save, rewind, fork (environment e continues from
    the state environment w reached), and a self-describing blob for files. A restored batch continues BIT FOR BIT as the batch that

@@ -29,6 +29,11 @@ class Stats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class MlpPolicyStruct(C.Structure):
+    """``lm_mlp_policy`` of include/locohip.h."""
+    _fields_ = [("n_layers", C.c_int), ("sizes", C.c_int * 4), ("activation", C.c_int), ("d_params", C.c_void_p), ("d_log_std", C.c_void_p)]
+
+
 class ForwardOut(C.Structure):
     _fields_ = [(n, _F) for n in ("M", "qfrc_bias", "qfrc_smooth", "qacc_smooth", "qacc", "qfrc_constraint")] + \
                [("ncon", C.POINTER(C.c_int)), ("solver_iter", C.POINTER(C.c_int))]
@@ -39,7 +44,7 @@ EXPORTS = ["lm_device_count", "lm_last_error", "lm_toolchain", "lm_lds_bytes", "
            "lm_set_dof_params", "lm_get_dof_params", "lm_set_dof_randomization", "lm_set_goal", "lm_step", "lm_step_device",
            "lm_pinned_slot", "lm_set_obs_order", "lm_step_pinned",
            "lm_set_terminal_obs", "lm_get_terminal_obs", "lm_pinned_terminal_obs",
-           "lm_set_reset_table", "lm_set_auto_reset", "lm_rollout", "lm_rollout_fused", "lm_rollout_tape", "lm_forward_debug", "lm_get_stats", "lm_sync",
+           "lm_set_reset_table", "lm_set_auto_reset", "lm_rollout", "lm_rollout_fused", "lm_rollout_tape", "lm_rollout_policy", "lm_forward_debug", "lm_get_stats", "lm_sync",
            "lm_get_flags", "lm_set_model_variants", "lm_set_variant_index", "lm_get_variant_index", "lm_set_variant_rows",
            "lm_set_model_compiler", "lm_compile_models", "lm_get_model_draws", "lm_get_model_tables",
            "lm_snapshot_create", "lm_snapshot_destroy", "lm_snapshot_save", "lm_snapshot_restore", "lm_snapshot_bytes",
@@ -98,6 +103,8 @@ def load_library():
     lib.lm_rollout_fused.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(Stats)]
     lib.lm_rollout_tape.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_int, C.POINTER(Stats)]
+    lib.lm_rollout_policy.argtypes = [C.c_void_p, C.POINTER(MlpPolicyStruct), C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(Stats)]
     lib.lm_forward_debug.argtypes = [C.c_void_p, _F, C.POINTER(ForwardOut)]
     lib.lm_get_stats.argtypes = [C.c_void_p, C.POINTER(Stats), C.c_int]
     lib.lm_sync.argtypes = [C.c_void_p]
@@ -206,6 +213,163 @@ def check_tape_args(n, nu, nobs, actions, obs=None, reward=None, done=None, term
     if spl < 1:
         raise ValueError("rollout_tape: steps_per_launch must be >= 1, not %d" % spl)
     return T, stride, spl
+
+
+POLICY_MAX_LAYERS, POLICY_MAX_WIDTH = 3, 256          # include/locohip.h lm_mlp_policy
+POLICY_ACTIVATIONS = {"tanh": 0, "relu": 1}
+
+
+def _check_policy_tensor(name, x, count):
+    """``x``: an object with ``shape`` / ``dtype`` / ``is_contiguous()`` / ``data_ptr()``: float32, ``count`` elements, contiguous, on the device."""
+    if not hasattr(x, "data_ptr"):
+        raise ValueError("MlpPolicy: %s must be a device tensor (data_ptr()), not %s" % (name, type(x).__name__))
+    if "float32" not in str(x.dtype):
+        raise ValueError("MlpPolicy: %s must be float32, not %s" % (name, x.dtype))
+    if len(x.shape) != 1 or int(x.shape[0]) != count:
+        raise ValueError("MlpPolicy: %s must be a flat tensor of %d elements, not %s" % (name, count, list(x.shape)))
+    if not x.is_contiguous():
+        raise ValueError("MlpPolicy: %s must be contiguous" % name)
+    if hasattr(x, "is_cuda") and not x.is_cuda:
+        raise ValueError("MlpPolicy: %s must live on the device" % name)
+
+
+class MlpPolicy:
+    """A small MLP policy for :meth:`HipBatch.rollout_policy` (``lm_mlp_policy``): ``sizes`` = (nobs, hidden widths ..., nu) with one
+    to three linear layers and hidden widths 1..256, ``activation`` "tanh" or "relu" after every layer but the last, ``params`` ONE
+    flat float32 device tensor — per layer W [out, in] row-major, then b [out]: ``torch.nn.utils.parameters_to_vector`` of a
+    ``Sequential(Linear, act, Linear, act, Linear)`` — and ``log_std`` None (deterministic) or a float32 device tensor [nu]. The
+    kernel reads both tensors in place at every step: an optimiser that updates them in place needs no further call. The object keeps
+    references to the tensors and nothing else."""
+
+    def __init__(self, sizes, activation, params, log_std=None):
+        self.sizes = tuple(int(v) for v in sizes)
+        if isinstance(activation, str):
+            if activation not in POLICY_ACTIVATIONS:
+                raise ValueError("MlpPolicy: activation must be 'tanh' or 'relu', not %r" % (activation,))
+            activation = POLICY_ACTIVATIONS[activation]
+        self.activation = int(activation)
+        if self.activation not in (0, 1):
+            raise ValueError("MlpPolicy: activation must be 0 (tanh) or 1 (relu), not %d" % self.activation)
+        n_layers = len(self.sizes) - 1
+        if n_layers < 1 or n_layers > POLICY_MAX_LAYERS:
+            raise ValueError("MlpPolicy: %d linear layers; one to %d are supported" % (n_layers, POLICY_MAX_LAYERS))
+        for w in self.sizes[1:-1]:
+            if w < 1 or w > POLICY_MAX_WIDTH:
+                raise ValueError("MlpPolicy: hidden width %d is outside 1..%d" % (w, POLICY_MAX_WIDTH))
+        for name, w in (("nobs", self.sizes[0]), ("nu", self.sizes[-1])):
+            if w < 1 or w > POLICY_MAX_WIDTH:
+                raise ValueError("MlpPolicy: %s = %d is outside 1..%d" % (name, w, POLICY_MAX_WIDTH))
+        _check_policy_tensor("params", params, self.n_params(self.sizes))
+        if log_std is not None:
+            _check_policy_tensor("log_std", log_std, self.sizes[-1])
+        self.params, self.log_std = params, log_std
+
+    @staticmethod
+    def n_params(sizes):
+        return sum(int(a) * int(b) + int(b) for a, b in zip(sizes[:-1], sizes[1:]))
+
+    @property
+    def n_layers(self):
+        return len(self.sizes) - 1
+
+    @classmethod
+    def from_torch(cls, sequential, log_std=None):
+        """From a ``torch.nn.Sequential`` of Linear layers (with bias) separated by ONE kind of activation, ``nn.Tanh`` or ``nn.ReLU``,
+        and ending in a Linear layer; anything else is refused. Where the module's parameters are already consecutive views of one flat
+        float32 tensor (as after ``p.data = flat[a:b].view_as(p)``), that storage is used in place; otherwise they are flattened ONCE
+        (``parameters_to_vector``) and the copy is kept in ``policy.params`` — re-create the policy after an optimiser step then."""
+        import torch
+        mods = list(sequential)
+        if not mods or len(mods) % 2 != 1:
+            raise ValueError("MlpPolicy.from_torch: expected Linear (, activation, Linear)*, got %d modules" % len(mods))
+        linears, acts = mods[0::2], mods[1::2]
+        for m in linears:
+            if not isinstance(m, torch.nn.Linear):
+                raise ValueError("MlpPolicy.from_torch: expected a Linear layer, found %s" % type(m).__name__)
+            if m.bias is None:
+                raise ValueError("MlpPolicy.from_torch: Linear layers need a bias")
+        kinds = {type(m) for m in acts}
+        if not kinds <= {torch.nn.Tanh, torch.nn.ReLU}:
+            raise ValueError("MlpPolicy.from_torch: activations must be nn.Tanh or nn.ReLU, found %s" % sorted(k.__name__ for k in kinds))
+        if len(kinds) > 1:
+            raise ValueError("MlpPolicy.from_torch: one kind of activation per policy, found Tanh and ReLU")
+        for a, b in zip(linears[:-1], linears[1:]):
+            if a.out_features != b.in_features:
+                raise ValueError("MlpPolicy.from_torch: layer widths do not chain: %d -> %d" % (a.out_features, b.in_features))
+        sizes = [linears[0].in_features] + [m.out_features for m in linears]
+        activation = 1 if kinds == {torch.nn.ReLU} else 0
+        ps = [p for m in linears for p in (m.weight, m.bias)]
+        for p in ps:
+            if p.dtype != torch.float32:
+                raise ValueError("MlpPolicy.from_torch: parameters must be float32, not %s" % p.dtype)
+            if not p.is_contiguous():
+                raise ValueError("MlpPolicy.from_torch: parameters must be contiguous")
+            if not p.is_cuda:
+                raise ValueError("MlpPolicy.from_torch: parameters must live on the device")
+        flat, at = None, ps[0].data_ptr()
+        in_place = True
+        for p in ps:
+            in_place = in_place and p.data_ptr() == at and p.untyped_storage().data_ptr() == ps[0].untyped_storage().data_ptr()
+            at += 4 * p.numel()
+        if in_place:
+            flat = torch.as_strided(ps[0].detach(), (cls.n_params(sizes),), (1,))
+        else:
+            flat = torch.nn.utils.parameters_to_vector(ps).detach().contiguous()
+        policy = cls(sizes, activation, flat, log_std.detach() if hasattr(log_std, "detach") else log_std)
+        policy.module = sequential
+        return policy
+
+    def struct(self):
+        st = MlpPolicyStruct()
+        st.n_layers = self.n_layers
+        for i, w in enumerate(self.sizes):
+            st.sizes[i] = w
+        st.activation = self.activation
+        st.d_params = int(self.params.data_ptr())
+        st.d_log_std = int(self.log_std.data_ptr()) if self.log_std is not None else None
+        return st
+
+
+def check_policy_args(n, nu, nobs, policy, n_steps, obs0=None, actions=None, obs=None, reward=None, done=None, terminal=None,
+                      steps_per_launch=None, terminal_enabled=True):
+    """The argument checks of :meth:`HipBatch.rollout_policy`, without a device: returns ``(T, steps_per_launch)`` or raises ValueError.
+    Buffers are described objects (torch tensors), which are checked, or raw device pointers (ints), which are taken as given."""
+    if not isinstance(policy, MlpPolicy):
+        raise ValueError("rollout_policy: policy must be an MlpPolicy, not %s" % type(policy).__name__)
+    if policy.sizes[0] != nobs:
+        raise ValueError("rollout_policy: the policy reads %d inputs, the model's observation has nobs = %d" % (policy.sizes[0], nobs))
+    if policy.sizes[-1] != nu:
+        raise ValueError("rollout_policy: the policy writes %d outputs, the model's action has nu = %d" % (policy.sizes[-1], nu))
+    if isinstance(n_steps, bool) or not isinstance(n_steps, (int, np.integer)) or int(n_steps) < 1:
+        raise ValueError("rollout_policy: n_steps must be an integer >= 1, not %r" % (n_steps,))
+    T = int(n_steps)
+
+    def described(x):
+        return hasattr(x, "data_ptr")
+
+    for name, x, shape, dtype in (("obs0", obs0, (n, nobs), "float32"), ("actions", actions, (T, n, nu), "float32"),
+                                  ("obs", obs, (T, n, nobs), "float32"), ("reward", reward, (T, n), "float32"), ("done", done, (T, n), "uint8"),
+                                  ("terminal", terminal, (T, n, nobs), "float32")):
+        if x is None:
+            continue
+        if not described(x):
+            if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
+                raise ValueError("rollout_policy: %s must be a device tensor (data_ptr()) or a raw device pointer (int), not %s" % (name, type(x).__name__))
+            continue
+        if tuple(x.shape) != tuple(shape):
+            raise ValueError("rollout_policy: %s must be %s, not %s" % (name, list(shape), list(x.shape)))
+        if dtype not in str(x.dtype):
+            raise ValueError("rollout_policy: %s must be %s, not %s" % (name, dtype, x.dtype))
+        if not x.is_contiguous():
+            raise ValueError("rollout_policy: %s must be contiguous" % name)
+        if hasattr(x, "is_cuda") and not x.is_cuda:
+            raise ValueError("rollout_policy: %s must live on the device" % name)
+    if terminal is not None and not terminal_enabled:
+        raise ValueError("rollout_policy: a terminal tape needs terminal observations enabled (enable_terminal_obs)")
+    spl = T if steps_per_launch is None else int(steps_per_launch)
+    if spl < 1:
+        raise ValueError("rollout_policy: steps_per_launch must be >= 1, not %d" % spl)
+    return T, spl
 
 
 SNAPSHOT_BLOB_HEADER = 64          # bytes in front of the payload of lm_snapshot_export (include/locohip.h)
@@ -664,6 +828,29 @@ class HipBatch:
         _check(self._lib.lm_rollout_tape(self._h, T, spl, _dev_ptr(actions), stride, _dev_ptr(obs), _dev_ptr(reward), _dev_ptr(done), _dev_ptr(terminal),
                                          _stream_ptr(stream), int(bool(sync)), C.byref(st) if sync else None))
         return st.as_dict() if sync else None
+
+    def rollout_policy(self, policy, n_steps, obs0=None, actions=None, obs=None, reward=None, done=None, terminal=None,
+                       steps_per_launch=None, noise_seed=0, stream=None, sync=True):
+        """``n_steps`` control steps in closed loop under an :class:`MlpPolicy`, evaluated on the device at the top of every step from
+        the observation the step before wrote (``lm_rollout_policy``). ``obs0`` float32 [n, nobs]: what the FIRST action is computed
+        from, in the kernel's column order (what :meth:`step_device` writes); None = the batch's own last-step row, valid after any
+        step but not after :meth:`set_state`. ``actions`` float32 [T, n, nu] receives every step's action (the raw one, before the
+        actuator's clamp) and is allocated when not given (needs a policy of torch tensors); ``obs`` / ``reward`` / ``done`` /
+        ``terminal``, ``steps_per_launch``, ``stream`` and ``sync`` as in :meth:`rollout_tape`. With ``policy.log_std`` the action is
+        mean + exp(log_std) * z, z keyed by (``noise_seed``, global environment id, the batch's step count, output index). Feeding the
+        returned tape to :meth:`rollout_tape` repeats the rollout bit for bit. Returns the action tape; the statistics of a
+        synchronous call are in ``self.last_policy_stats``."""
+        T, spl = check_policy_args(self.n, self.nu, self.nobs, policy, n_steps, obs0, actions, obs, reward, done, terminal, steps_per_launch,
+                                   terminal_enabled=self._term_on)
+        if actions is None:
+            import torch
+            actions = torch.empty((T, self.n, self.nu), dtype=torch.float32, device=policy.params.device)
+        st, ps = Stats(), policy.struct()
+        _check(self._lib.lm_rollout_policy(self._h, C.byref(ps), T, spl, int(noise_seed) & 0xFFFFFFFFFFFFFFFF, _dev_ptr(obs0), _dev_ptr(actions),
+                                           _dev_ptr(obs), _dev_ptr(reward), _dev_ptr(done), _dev_ptr(terminal),
+                                           _stream_ptr(stream), int(bool(sync)), C.byref(st) if sync else None))
+        self.last_policy_stats = st.as_dict() if sync else None
+        return actions
 
     # ---- snapshots (include/locohip.h lm_snapshot_*)
     def snapshot_signature(self):

@@ -1,5 +1,6 @@
 // lm_family.hip — one kernel family (LM_FAMILY) and part (LM_PART) of the step kernels; see lm_step.h.
-// The library links one object per family and part (three parts per row of lm_families.h; part 2 of the generic family holds nothing) so that `make -j`
+// The library links one object per family and part (five parts per row of lm_families.h: 0-2 the kernel kinds' parts, 3 and 4 the policy
+// kernels of the fused and of the replay kinds; parts 2-4 of the generic family hold nothing) so that `make -j`
 // builds them in parallel.
 #include "lm_step.h"
 
@@ -10,7 +11,14 @@ namespace lmk {
 bool LM_CAT(launch_f, LM_FAMILY, p, LM_PART)(const LaunchCtx& L0, const KArgs& a, int kind) {
   constexpr Family F = family(LM_FAMILY);      // the family's row (lm_families.h): everything its kernels are compiled for
   static_assert(F.present, "LM_FAMILY is not a row of LM_FAMILY_LIST");
+#if LM_PART >= 3
+  // the POLICY instantiations of the fused and replay kinds (lm_step.h launch_family_policy); the generic family has no fused kernels
 #if LM_FAMILY != LM_GENERIC_FAMILY
+  return launch_family_policy<F.MC, F.NS, F.RK4, F.CONE, F.NM, LM_PART, F.PM>(L0, a, kind);
+#else
+  return false;
+#endif
+#elif LM_FAMILY != LM_GENERIC_FAMILY
   return launch_family<F.MC, F.NS, F.RK4, F.CONE, F.NM, LM_PART, F.PM>(L0, a, kind);
 #elif LM_PART == 2
   return false;          // the generic family has no kernels with per-environment parameters

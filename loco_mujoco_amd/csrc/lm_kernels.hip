@@ -5,6 +5,7 @@
 #include "lm_compile.h"
 #include "lm_snapshot.h"
 #include "lm_model_parse.h"
+#include "lm_policy.h"
 #include <memory>
 
 using lmk::KArgs; using lmk::Task; using lmk::DevStats; using lmk::LaunchCtx;
@@ -77,11 +78,42 @@ struct lm_batch {
   // terminal observations (lm_set_terminal_obs, lm_step.h KArgs::term_obs): the buffer the kernels write (null: off), the one the batch
   // owns (null with a caller's buffer), and the fourth array of every pinned result set, [N][nobs] float64 (lm_pinned_terminal_obs)
   float *term_obs, *term_own; double* h_term64[LM_PINNED_SLOTS];
+  // policy rollouts (lm_rollout_policy, lm_step.h KArgs::pol): the lanes' hand-over rows [N][2 * lmp::kPolicyMaxWidth] and, for batches
+  // that collect no terminal observations, the sink [N][nobs] the policy kernels' terminal store writes to (they are compiled with
+  // that store only). Scratch of a launch, allocated by the first policy call: nothing of it is state, nothing enters a snapshot
+  float *pol_hand, *pol_sink;
   // every device or pinned array above that the batch owns: its field's address, entered by batch_array where the array is allocated.
   // lm_batch_destroy releases what these fields hold at that moment and names none of them
   struct Owned { void** field; bool pinned; };
   std::vector<Owned> owned;
 };
+namespace lmp {
+// policy_row for every (active) environment: 4 environments per wave-sized workgroup, 16 lanes each. Used in front of every control
+// step that runs as a launch of its own; the step kernel then reads the action row in action_mode 0, on the same stream.
+struct PolicyArgs {
+  lm_mlp_policy p;
+  const float* obs;          // [N][nobs]: the observation the action is computed from
+  float* act;                // [N][nu]: this control step's row of the action tape
+  const int* env_map; int n_active;      // the active list (lm_step.h KArgs): slot -> environment, or null
+  unsigned long long noise_seed; long long env_offset; unsigned step_index;
+};
+
+__global__ __launch_bounds__(64) void policy_kernel(PolicyArgs a) {
+  __shared__ float hand[4][2 * kPolicyMaxWidth];
+  const int lane = threadIdx.x & 15, e_local = threadIdx.x >> 4;
+  const int slot = blockIdx.x * 4 + e_local;
+  if (slot >= a.n_active) return;           // (nothing below joins the whole workgroup)
+  const int e = a.env_map ? a.env_map[slot] : slot;
+  const int nobs = a.p.sizes[0], nu = a.p.sizes[a.p.n_layers];
+  policy_row(a.p, a.obs + (long long)e * nobs, a.act + (long long)e * nu, hand[e_local], lane, a.noise_seed, a.env_offset + e, a.step_index);
+}
+
+static void launch_policy(const PolicyArgs& a, hipStream_t stream) {
+  if (a.n_active <= 0) return;
+  hipLaunchKernelGGL(policy_kernel, dim3((a.n_active + 3) / 4), dim3(64), 0, stream, a);
+}
+}  // namespace lmp
+
 // A/B switches of the probe builds (tools/probes: `make EXTRA=-DLM_PROBES ...`). The shipped library reads NO environment variable:
 // tests/test_abi_exports.py checks that `getenv` is not among its undefined symbols.
 #ifdef LM_PROBES
@@ -128,8 +160,9 @@ template <class T> static int batch_array(lm_batch* b, T** field, size_t count, 
 }
 
 // the launch functions of the lm_family.hip objects, [family][part]: from the one list of families (absent ids: null)
-static lmk::family_fn kFamilyTable[lmk::LMK_NFAMILY][3];
-#define LM_X(id, ...) kFamilyTable[id][0] = lmk::launch_f##id##p0; kFamilyTable[id][1] = lmk::launch_f##id##p1; kFamilyTable[id][2] = lmk::launch_f##id##p2;
+static lmk::family_fn kFamilyTable[lmk::LMK_NFAMILY][5];
+#define LM_X(id, ...) kFamilyTable[id][0] = lmk::launch_f##id##p0; kFamilyTable[id][1] = lmk::launch_f##id##p1; kFamilyTable[id][2] = lmk::launch_f##id##p2; \
+  kFamilyTable[id][3] = lmk::launch_f##id##p3; kFamilyTable[id][4] = lmk::launch_f##id##p4;
 static const bool kFamilyTableFilled = [] { LM_FAMILY_LIST(LM_X) return true; }();
 #undef LM_X
 
@@ -192,7 +225,9 @@ static void launch_variant(lm_batch* b, const KArgs& a, hipStream_t stream) {
   }
   const int kind = lmk::pick_kind(FWD, a.nfused > 1, b->nvar > 0, b->dofprm != nullptr, b->epb <= 4 && !replicas_off());
   const int big = lmk::find_kind(b->nvar > 0 ? 2 : (b->dofprm ? 1 : 0), lmk::kReplay, true);
-  const lmk::family_fn launch = kFamilyTable[fam][lmk::kKinds[kind].part], launch_big = kFamilyTable[fam][lmk::kKinds[big].part];
+  // (a policy launch, KArgs::pol: the same kinds from the parts that hold their POLICY instantiations, lm_step.h launch_family_policy)
+  const bool policy = a.pol.d_params != nullptr;
+  const lmk::family_fn launch = kFamilyTable[fam][policy ? 3 : lmk::kKinds[kind].part], launch_big = kFamilyTable[fam][policy ? 4 : lmk::kKinds[big].part];
   KArgs r = a;
   r.reg_grid = (b->n_active + b->epb - 1) / b->epb; r.epoch = b->epoch; r.host_hint = b->h_hint;
   const bool replay = !FWD && a.replay_list;
@@ -870,10 +905,19 @@ static StepIO own_rows(lm_batch* b, int action_mode, const float* action) {
 // THE launch path of lm_step*, lm_rollout_fused and lm_rollout_tape: queues `n_steps` control steps on `stream`, `steps_per_launch` of
 // them per launch. b->step_index, the count that keys the random actions, advances by the launches that were accepted and by no
 // other: a refused call leaves it where it was. `timed`: ev0 / ev1 around the span
-static int queue_steps(lm_batch* b, hipStream_t stream, const StepIO& io, int n_steps, int steps_per_launch, bool timed) {
+// `pol` (lm_rollout_policy): the control steps take their actions from a policy, evaluated from the observation the step before left
+// (pol->obs0 for the call's first step). A launch of several control steps: the POLICY instantiation of the fused kernel does it at the
+// top of every step (lm_step.h KArgs::pol). A launch of ONE control step (the layouts and families without a fused kernel, the model
+// compiler, a ragged last launch): policy_kernel (lm_policy.h) writes the step's row of the action tape in front of the ordinary
+// launch, on the same stream. Both run lmp::policy_row: the actions are bitwise the same either way
+struct PolicyCall { lm_mlp_policy p; const float* obs0; unsigned long long noise_seed; };
+static int queue_steps(lm_batch* b, hipStream_t stream, const StepIO& io, int n_steps, int steps_per_launch, bool timed, const PolicyCall* pol = nullptr) {
   // one control step per launch where there is no fused kernel (the full-wave layout, the generic family), and with the model compiler:
   // a restart inside a launch needs its fresh model before the episode's first step. The launch's pointers then carry the offsets
   if (b->epb > 4 || replicas_off() || one_layout_only(b) || b->mc_ib) steps_per_launch = 1;
+#ifdef LM_NO_POLICY_KERNELS
+  if (pol) steps_per_launch = 1;      // a library built without the POLICY instantiations (lm_step.h): policy_kernel in front of every step
+#endif
   KArgs a = make_args(b);
   a.action_mode = io.action_mode; a.seed = io.seed;
   a.tape_action = io.action_stride; a.tape_obs = io.obs_stride; a.tape_reward = io.reward_stride; a.tape_done = io.done_stride; a.tape_term = io.term_stride;
@@ -888,6 +932,18 @@ static int queue_steps(lm_batch* b, hipStream_t stream, const StepIO& io, int n_
     // attributes ...): drop what they left behind so that the check after the launch reports OUR launch
     (void)hipGetLastError();
     g_launch_err = nullptr;
+    if (pol) {
+      const float* prev = s == 0 ? pol->obs0 : io.obs + (s - 1) * io.obs_stride;
+      a.pol.d_params = nullptr;
+      if (a.nfused > 1) {
+        a.pol = pol->p; a.pol_obs0 = prev; a.pol_seed = pol->noise_seed; a.pol_hand = b->pol_hand;
+        if (!a.term_obs) a.term_obs = b->pol_sink;
+      } else {
+        if (!io.term) a.term_obs = b->term_obs;        // (not the sink of an earlier fused launch of this call)
+        lmp::PolicyArgs pa = {pol->p, prev, const_cast<float*>(a.action), b->env_map, b->n_active, pol->noise_seed, b->env_offset, b->step_index};
+        lmp::launch_policy(pa, stream);
+      }
+    }
     launch_variant<false>(b, a, stream);
     if (g_launch_err) return fail(g_launch_err);
     // the environments that restarted an episode in this launch get their fresh model before the next one (stream order)
@@ -1156,6 +1212,53 @@ int lm_rollout_tape(lm_batch* b, int n_steps, int steps_per_launch, const float*
   if (d_term) { io.term = d_term; io.term_stride = N * T.nobs; }
   StreamScope scope(b, stream);
   if (scope.enter() || queue_steps(b, scope.used, io, n_steps, steps_per_launch, true) || scope.leave()) return 1;
+  if (!sync) return 0;
+  HIPCHK(hipEventSynchronize(b->ev1));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, b->ev0, b->ev1));
+  b->acc.kernel_ms += ms;
+  if (stats) {
+    if (drain_stats(b)) return 1;
+    *stats = b->acc; stats->kernel_ms = ms;
+  }
+  return 0;
+}
+
+int lm_rollout_policy(lm_batch* b, const lm_mlp_policy* p, int n_steps, int steps_per_launch, uint64_t noise_seed,
+                      const float* d_obs0, float* d_actions, float* d_obs, float* d_reward, uint8_t* d_done,
+                      float* d_term, void* stream, int sync, lm_stats* stats) {
+  if (!b) return fail("null batch");
+  HIPCHK(hipSetDevice(b->m->device));
+  const long long N = b->N; const Task& T = b->m->T;
+  // every argument is checked before the first launch: a refused call leaves the batch as it was
+  if (!p) return fail("lm_rollout_policy: the policy is null");
+  if (n_steps < 0) return fail("lm_rollout_policy: n_steps must be >= 0");
+  if (steps_per_launch < 1) return fail("lm_rollout_policy: steps_per_launch must be >= 1");
+  if (p->n_layers < 1 || p->n_layers > lmp::kPolicyMaxLayers) return fail("lm_rollout_policy: n_layers must be 1..3");
+  if (p->sizes[0] != T.nobs) return fail("lm_rollout_policy: sizes[0] = " + std::to_string(p->sizes[0]) + ", the model's nobs = " + std::to_string(T.nobs));
+  if (p->sizes[p->n_layers] != T.nu) return fail("lm_rollout_policy: sizes[n_layers] = " + std::to_string(p->sizes[p->n_layers]) + ", the model's nu = " + std::to_string(T.nu));
+  for (int l = 1; l < p->n_layers; l++)
+    if (p->sizes[l] < 1 || p->sizes[l] > lmp::kPolicyMaxWidth) return fail("lm_rollout_policy: hidden width " + std::to_string(p->sizes[l]) + " is outside 1..256");
+  if (T.nobs > lmp::kPolicyMaxWidth || T.nu > lmp::kPolicyMaxWidth) return fail("lm_rollout_policy: nobs and nu must be at most 256");
+  if (p->activation != 0 && p->activation != 1) return fail("lm_rollout_policy: activation must be 0 (tanh) or 1 (relu)");
+  if (!p->d_params) return fail("lm_rollout_policy: d_params is null");
+  if (!d_actions) return fail("lm_rollout_policy: d_actions is null (the action tape is the output and what the steps read)");
+  if (d_term && !b->term_obs) return fail("lm_rollout_policy: d_term needs terminal observations enabled (lm_set_terminal_obs)");
+  if (b->lds_ok[0] != b->epb) {          // (what the first launch would refuse, before the policy's kernel is queued)
+    const std::string why = layout_refusal(b, b->epb, false);
+    if (!why.empty()) return fail(why);
+  }
+  if (!b->pol_hand && batch_array(b, &b->pol_hand, (size_t)N * 2 * lmp::kPolicyMaxWidth)) return 1;
+  if (!b->pol_sink && batch_array(b, &b->pol_sink, (size_t)N * T.nobs)) return 1;
+  StepIO io = own_rows(b, 0, d_actions);
+  io.action_stride = N * T.nu;
+  if (d_obs) { io.obs = d_obs; io.obs_stride = N * T.nobs; }
+  if (d_reward) { io.reward = d_reward; io.reward_stride = N; }
+  if (d_done) { io.done = d_done; io.done_stride = N; }
+  if (d_term) { io.term = d_term; io.term_stride = N * T.nobs; }
+  const PolicyCall pol = {*p, d_obs0 ? d_obs0 : b->obs, noise_seed};
+  StreamScope scope(b, stream);
+  if (scope.enter() || queue_steps(b, scope.used, io, n_steps, steps_per_launch, true, &pol) || scope.leave()) return 1;
   if (!sync) return 0;
   HIPCHK(hipEventSynchronize(b->ev1));
   float ms = 0;

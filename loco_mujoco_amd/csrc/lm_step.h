@@ -46,6 +46,7 @@ __device__ __forceinline__ int lm_opaque_zero() { int z = 0; asm volatile("" : "
 #include "lm_core.h"
 #include "lm_families.h"
 #include "../../include/locohip.h"
+#include "lm_policy.h"
 
 namespace lmk {
 
@@ -202,6 +203,12 @@ struct KArgs {
   // N | N | N*nobs. 0 (the default, and the stride of a null pointer) = every step uses the same rows: the policy-free rollouts,
   // action repeat, outputs that are not recorded.
   long long tape_action, tape_obs, tape_reward, tape_done, tape_term;
+  // POLICY (lm_rollout_policy; read by the POLICY instantiations of the FUSED kernels only, chosen at launch by pol.d_params != null —
+  // behind every other field, like term_obs was: no other offset moves). At the top of control step `fused` the 16 lanes of an
+  // environment evaluate the MLP (lm_policy.h policy_row) on pol_obs0 (fused == 0: the observation the launch starts from) or on the row
+  // the step before stored (obs + (fused - 1) * tape_obs) and write row `fused` of the action tape, which the step then reads as any
+  // tape action. pol_hand: [N][2 * lmp::kPolicyMaxWidth] floats, the lanes' hand-over of hidden activations (scratch of a launch).
+  lm_mlp_policy pol; const float* pol_obs0; unsigned long long pol_seed; float* pol_hand;
 };
 
 __device__ __forceinline__ unsigned long long mix64(unsigned long long x) {
@@ -265,7 +272,7 @@ __device__ __forceinline__ int replay_next(const KArgs& a, int& cursor) {
   }
 }
 
-template <int MC, int NS, bool RK4, bool FORWARD_ONLY, int CONE = -1, int NM = 0, int DR = 0, int REP = 1, bool FUSED = false, int PM = 0, bool TERM = false>
+template <int MC, int NS, bool RK4, bool FORWARD_ONLY, int CONE = -1, int NM = 0, int DR = 0, int REP = 1, bool FUSED = false, int PM = 0, bool TERM = false, bool POLICY = false>
 __global__ __launch_bounds__(64) void step_kernel(KArgs a) {
   using QuadDpp = QuadDppT<REP>;
   constexpr bool PAIRS = PM != 0;
@@ -358,6 +365,23 @@ __global__ __launch_bounds__(64) void step_kernel(KArgs a) {
   float* const obs_k = FUSED ? a.obs + fused * a.tape_obs : a.obs;
   float* const reward_k = FUSED ? a.reward + fused * a.tape_reward : a.reward;
   unsigned char* const done_k = FUSED ? a.done + fused * a.tape_done : a.done;
+  if constexpr (POLICY) {
+    // POLICY instantiations only (KArgs::pol, chosen at launch): this control step's action, computed here by the environment's 16 lanes
+    // (4 replicas x 4 chains in the regular kernels, the whole workgroup in the replay kernel: threadIdx.x & 15 either way) from the
+    // observation the step before left, and recorded in row `fused` of the action tape — the actuator path and the muscle-control path
+    // below read it there as they read any tape action. Everything outside this block is, token for token, the kernel without the
+    // feature (see the TERM block below, and for the same reason). An environment that left for the replay kernel computes no more
+    // actions here; the replay kernel finds the hand-over step's action in the tape (stored before the __threadfence() that lists the
+    // environment) and evaluates the policy from the step after it. Padding quads compute nothing: they read the row of the environment
+    // they shadow, which sits in this wave.
+    static_assert(FUSED && TERM, "policy kernels are the fused kinds, compiled with the terminal-observation store");
+    if (in_range && !gone && (!REPLAY || fused > first_step)) {
+      const float* prev = (fused == 0 ? a.pol_obs0 : a.obs + (fused - 1) * a.tape_obs) + (long long)e * a.T.nobs;
+      float* row = const_cast<float*>(a.action) + fused * a.tape_action + (long long)e * a.T.nu;
+      lmp::policy_row<true>(a.pol, prev, row, a.pol_hand + (long long)e * (2 * lmp::kPolicyMaxWidth), (int)(threadIdx.x & 15), a.pol_seed, a.env_offset + e, step_index);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");      // the row is read by lanes that did not write it
+  }
   bool valid = valid0 && !gone && (!REPLAY || fused >= first_step);
   // ---- load state (root replicated in the 4 lanes: same address -> one transaction)
   float qr[6], vr[6], war[6], qc[MC], vc[MC], wac[MC], goal[4];
@@ -895,9 +919,44 @@ static bool launch_family(const LaunchCtx& L0, const KArgs& a, int kind) {
   return false;
 }
 
-// defined in the lm_family.hip objects, three parts per family of lm_families.h; false = this family/part has no kernel of that kind
+// POLICY launches (KArgs::pol.d_params != null, lm_rollout_policy): the POLICY instantiations of the fused kinds, compiled WITH the
+// terminal-observation store only (lm_kernels.hip points term_obs at a sink of the batch's when nobody collects terminal observations).
+// They live in objects of their own, so that no object of the default kernels takes longer to build than it did: part 3 = the three
+// regular fused kinds (geometry and lane memory of launch_regular), part 4 = the three replay kinds (those of launch_family's replay
+// branch). -DLM_NO_POLICY_KERNELS: a library without them — the -O2 guard build, which exists to compare the DEFAULT kernels' physics
+// at another optimisation level; lm_kernels.hip then runs every policy step as policy_kernel + a launch of its own.
+template <int MC, int NS, bool RK4, int CONE, int NM, int PART, int PM = 0>
+static bool launch_family_policy(const LaunchCtx& L0, const KArgs& a, int kind) {
+#ifndef LM_NO_POLICY_KERNELS
+  static_assert(PART == 3 || PART == 4, "the policy kernels' parts");
+  LaunchCtx L = L0;
+  L.stat_bytes = static_lds_bytes(NM);
+  if (kind < 0 || kind >= LMK_NKINDS || !kKinds[kind].fused || !a.pol.d_params) return false;
+  if constexpr (PART == 3) {
+    using LMm = lm::LaneMemFor<MC, NS, NM, (PM == 1 || PM == 2), CONE>;
+    const dim3 grid((L.N + L.epb - 1) / L.epb), block(16 * L.epb);      // (fused kinds: the replicated layout)
+#define LM_POLICY(K) if (kind == K) { launch_one(step_kernel<MC, NS, RK4, false, CONE, NM, kKinds[K].DR, 4, true, PM, true, true>, grid, block, (size_t)LMm::kGroup, L, a); return true; }
+    LM_POLICY(LMK_FUSED) LM_POLICY(LMK_FUSED_DR) LM_POLICY(LMK_FUSED_DRV)
+#undef LM_POLICY
+  } else {
+    constexpr int NSB = 128, PMB = (PM != 0) ? 1 : 0;
+    using LMb = lm::LaneMemFor<MC, NSB, NM, (PM != 0), CONE>;
+    KArgs b = a;
+    b.epb = 1; b.xcd_map = 0;
+    const int ngroups = (int)((L.N + a.epb - 1) / a.epb), want = L.epb;      // (as in launch_family's replay branch)
+    const dim3 grid(ngroups < want ? ngroups : want), block(4 * kReplayRep);
+#define LM_POLICY(K) if (kind == K) { launch_one(step_kernel<MC, NSB, RK4, false, CONE, NM, kKinds[K].DR, kReplayRep, true, PMB, true, true>, grid, block, (size_t)LMb::kPadded * 4, L, b); return true; }
+    LM_POLICY(LMK_BIG) LM_POLICY(LMK_BIG_DR) LM_POLICY(LMK_BIG_DRV)
+#undef LM_POLICY
+  }
+#endif
+  return false;
+}
+
+// defined in the lm_family.hip objects, five parts per family of lm_families.h (0-2: the kinds' parts, 3 / 4: the policy kernels); false = this family/part has no kernel of that kind
 typedef bool (*family_fn)(const LaunchCtx&, const KArgs&, int kind);
-#define LM_X(id, ...) bool launch_f##id##p0(const LaunchCtx&, const KArgs&, int); bool launch_f##id##p1(const LaunchCtx&, const KArgs&, int); bool launch_f##id##p2(const LaunchCtx&, const KArgs&, int);
+#define LM_X(id, ...) bool launch_f##id##p0(const LaunchCtx&, const KArgs&, int); bool launch_f##id##p1(const LaunchCtx&, const KArgs&, int); bool launch_f##id##p2(const LaunchCtx&, const KArgs&, int); \
+  bool launch_f##id##p3(const LaunchCtx&, const KArgs&, int); bool launch_f##id##p4(const LaunchCtx&, const KArgs&, int);
 LM_FAMILY_LIST(LM_X)
 #undef LM_X
 
