@@ -40,6 +40,10 @@
  *                          recorded actions), with every step's observation, reward and done byte recorded
  *   lm_rollout_policy   <- the same loop with a policy inside, `a = policy(obs); obs, r, absorbing, _ = env.step(a)`: a small MLP evaluated
  *                          on the device at the top of every control step, its actions recorded as a tape
+ *   lm_set_policy_obs_norm <- the Standardizer in front of the reference's actor and critic (examples/imitation_learning/utils.py):
+ *                          the policy of lm_rollout_policy reads the clipped, standardised observation
+ *   lm_tape_gae         <- mushroom-rl's compute_gae over the dataset of one Core.learn epoch (the reference's PPO / TRPO baselines),
+ *                          over the tapes and with the done byte's bits told apart, one launch
  *   lm_forward_debug    <- mujoco.mj_forward (base.py:362) with intermediate results, for parity tests
  *   lm_snapshot_create / _save / _restore / _export / _import <- copy.copy(data) / mujoco.mj_copyData of every environment's MjData
  *                          (the reference keeps one MjData per environment on the host, base.py:185; it has no call of its own for
@@ -335,6 +339,37 @@ int lm_rollout_policy(lm_batch* b, const lm_mlp_policy* p, int n_steps, int step
                       const float* d_obs0, float* d_actions, float* d_obs, float* d_reward, uint8_t* d_done,
                       float* d_term, void* stream, int sync, lm_stats* stats);
 
+/* POLICY INPUT NORMALISATION (off by default): the policy of lm_rollout_policy reads clamp((obs - mean) * inv_std, -clip, clip) in place
+   of the raw observation row — the running standardiser in front of the reference's actors (examples/imitation_learning/utils.py
+   Standardizer) and of practically every locomotion PPO.
+   d_mean, d_inv_std: DEVICE float32 [nobs] in the KERNEL's column order (that of lm_step_device / d_obs0, not lm_set_obs_order's);
+   caller-owned, read in place at every policy evaluation like lm_mlp_policy.d_params (an update between two calls is seen by the next).
+   clip > 0: the normalised input is clamped to [-clip, clip]; clip == 0: no clamp. Both pointers NULL: off (the default).
+   One NULL and one not, clip < 0 or not finite: refused, nothing changes. Waits for the batch's launches in flight (as lm_set_terminal_obs).
+   Per input: one subtraction, one multiplication, two selects, each rounded on its own — torch's ((x - mean) * inv_std).clamp(-clip, clip)
+   bit for bit, a NaN staying NaN; both launch paths of lm_rollout_policy run it. Only what the policy reads is normalised: the observation
+   rows and tapes the steps write, the terminal rows and d_obs0 stay raw. With the setting off the actions are bitwise what they were. */
+int lm_set_policy_obs_norm(lm_batch* b, const float* d_mean, const float* d_inv_std, float clip);
+
+/* Generalised advantage estimation over the tapes of lm_rollout_tape / lm_rollout_policy, with the done byte's meaning built in
+   (the reference's training loop: mushroom-rl compute_gae with absorbing = done & 1, last = done != 0 or t == n_steps - 1).
+     d_reward [T][n] f32, d_done [T][n] bytes        the tapes
+     d_value  [T][n] f32                             V(the observation step t's action was computed from: obs0, then obs[t-1])
+     d_last_value [n] f32                            V(obs[T-1]): the successor of the last step where that step ended no episode
+     d_term_value [T][n] f32 or NULL                 V(terminal tape row), READ ONLY where done has bit 1 and not bit 0 (a truncation);
+                                                     NULL: such steps bootstrap with 0
+   next_v = 0 if done & 1; else d_term_value[t][e] if done & 2; else (t == T-1 ? d_last_value[e] : d_value[t+1][e])
+   delta  = r + gamma * next_v - v;  adv[t] = delta + (done != 0 || t == T-1 ? 0 : gamma * lam * adv[t+1]);  ret[t] = adv[t] + v
+   float32, one environment per lane, t from T-1 down, each line above one fmaf chain in the order written — delta = fmaf(gamma, next_v, r)
+   - v, adv[t] = fmaf(gamma * lam, adv[t+1], delta) with the product gamma * lam rounded once: the result does not depend on n, the
+   launch shape or the environment's place. What a cut makes unreachable (d_value[t+1], d_last_value, adv[t+1]) is selected away, not
+   multiplied by zero: a NaN there stays out. d_adv, d_ret [T][n] f32, either may be NULL (not both). All n_envs rows are computed,
+   active list or not. One launch on `stream`, ordered behind everything the batch has in flight as the snapshot copy is; stream, sync:
+   as lm_rollout_tape. Checked before the launch: null pointers, n_steps < 1, gamma / lam outside [0, 1] or not finite — a refused call
+   launches nothing. */
+int lm_tape_gae(lm_batch* b, int n_steps, const float* d_reward, const uint8_t* d_done, const float* d_value, const float* d_last_value,
+                const float* d_term_value, float gamma, float lam, float* d_adv, float* d_ret, void* stream, int sync);
+
 /* SNAPSHOTS: the state of every environment of a batch, kept in device memory — save, rewind, fork (environment e continues from
    the state environment w reached), and a self-describing blob for files. A restored batch continues BIT FOR BIT as the batch that
    was saved would have (lm_set_state cannot do that: it carries qpos / qvel only and clears the rest).
@@ -344,7 +379,7 @@ int lm_rollout_policy(lm_batch* b, const lm_mlp_policy* p, int n_steps, int step
    the environment's own slot of the inertial record / geom table / geom-pair table, its restart flag, draw counter and draws — the
    batch's last-step rows (observation, reward, done byte, validity flags), and the batch's count of control steps.
    It does NOT hold settings (the reset table, seed and horizon, the active list, the layout, the replay mode, the randomisation
-   spec, the variant pool, the compiler program), accumulators and diagnostics (lm_stats, replay marks, the pollers' hint, timers),
+   spec, the variant pool, the compiler program, the policy's input normalisation of lm_set_policy_obs_norm), accumulators and diagnostics (lm_stats, replay marks, the pollers' hint, timers),
    output buffers (the pinned ring, terminal-observation buffers of the library or the caller) or the scratch of a launch (the
    replay list and its control words, the resume states): every launch leaves those consumed.
      lm_snapshot_create   device storage sized for b's configuration NOW: n_envs, nv, na, nobs, the collider cache's pairs, whether

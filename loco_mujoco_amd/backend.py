@@ -44,7 +44,7 @@ EXPORTS = ["lm_device_count", "lm_last_error", "lm_toolchain", "lm_lds_bytes", "
            "lm_set_dof_params", "lm_get_dof_params", "lm_set_dof_randomization", "lm_set_goal", "lm_step", "lm_step_device",
            "lm_pinned_slot", "lm_set_obs_order", "lm_step_pinned",
            "lm_set_terminal_obs", "lm_get_terminal_obs", "lm_pinned_terminal_obs",
-           "lm_set_reset_table", "lm_set_auto_reset", "lm_rollout", "lm_rollout_fused", "lm_rollout_tape", "lm_rollout_policy", "lm_forward_debug", "lm_get_stats", "lm_sync",
+           "lm_set_reset_table", "lm_set_auto_reset", "lm_rollout", "lm_rollout_fused", "lm_rollout_tape", "lm_rollout_policy", "lm_set_policy_obs_norm", "lm_tape_gae", "lm_forward_debug", "lm_get_stats", "lm_sync",
            "lm_get_flags", "lm_set_model_variants", "lm_set_variant_index", "lm_get_variant_index", "lm_set_variant_rows",
            "lm_set_model_compiler", "lm_compile_models", "lm_get_model_draws", "lm_get_model_tables",
            "lm_snapshot_create", "lm_snapshot_destroy", "lm_snapshot_save", "lm_snapshot_restore", "lm_snapshot_bytes",
@@ -105,6 +105,9 @@ def load_library():
                                     C.c_void_p, C.c_int, C.POINTER(Stats)]
     lib.lm_rollout_policy.argtypes = [C.c_void_p, C.POINTER(MlpPolicyStruct), C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(Stats)]
+    lib.lm_set_policy_obs_norm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float]
+    lib.lm_tape_gae.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.lm_forward_debug.argtypes = [C.c_void_p, _F, C.POINTER(ForwardOut)]
     lib.lm_get_stats.argtypes = [C.c_void_p, C.POINTER(Stats), C.c_int]
     lib.lm_sync.argtypes = [C.c_void_p]
@@ -372,7 +375,119 @@ def check_policy_args(n, nu, nobs, policy, n_steps, obs0=None, actions=None, obs
     return T, spl
 
 
-SNAPSHOT_BLOB_HEADER = 64          # bytes in front of the payload of lm_snapshot_export (include/locohip.h)
+def _check_device_buffer(who, name, x, shape, dtype):
+    """``x``: a raw device pointer (int), taken as given, or a described object (torch tensor): ``shape``, ``dtype``, contiguous, on the device."""
+    if not hasattr(x, "data_ptr"):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
+            raise ValueError("%s: %s must be a device tensor (data_ptr()) or a raw device pointer (int), not %s" % (who, name, type(x).__name__))
+        return
+    if tuple(x.shape) != tuple(shape):
+        raise ValueError("%s: %s must be %s, not %s" % (who, name, list(shape), list(x.shape)))
+    if dtype not in str(x.dtype):
+        raise ValueError("%s: %s must be %s, not %s" % (who, name, dtype, x.dtype))
+    if not x.is_contiguous():
+        raise ValueError("%s: %s must be contiguous" % (who, name))
+    if hasattr(x, "is_cuda") and not x.is_cuda:
+        raise ValueError("%s: %s must live on the device" % (who, name))
+
+
+def check_obs_norm_args(nobs, mean, inv_std, clip):
+    """The argument checks of :meth:`HipBatch.set_policy_obs_norm`, without a device: returns ``clip`` as a float or raises ValueError.
+    ``mean`` / ``inv_std``: both None (off), or both float32 [nobs], contiguous, on the device — described objects (torch tensors), which
+    are checked, or raw device pointers (ints), which are taken as given. ``clip``: finite and >= 0 (0: no clamp)."""
+    who = "set_policy_obs_norm"
+    if (mean is None) != (inv_std is None):
+        raise ValueError("%s: mean and inv_std go together (both None: off)" % who)
+    if isinstance(clip, bool) or not isinstance(clip, (int, float, np.integer, np.floating)):
+        raise ValueError("%s: clip must be a number, not %s" % (who, type(clip).__name__))
+    clip = float(clip)
+    if not np.isfinite(clip) or clip < 0:
+        raise ValueError("%s: clip must be finite and >= 0 (0: no clamp), not %r" % (who, clip))
+    if mean is not None:
+        _check_device_buffer(who, "mean", mean, (nobs,), "float32")
+        _check_device_buffer(who, "inv_std", inv_std, (nobs,), "float32")
+    return clip
+
+
+def check_gae_args(n, reward, done, value, last_value, term_value=None, gamma=0.99, lam=0.95, adv=None, ret=None, n_steps=None):
+    """The argument checks of :meth:`HipBatch.gae`, without a device: returns ``(T, gamma, lam)`` or raises ValueError. Buffers are
+    described objects (torch tensors), which are checked — ``reward`` / ``value`` / ``term_value`` / ``adv`` / ``ret`` float32 [T, n],
+    ``done`` uint8 [T, n], ``last_value`` float32 [n] — or raw device pointers (ints), which are taken as given; T comes from the
+    first described tape, or from ``n_steps`` when every tape is a raw pointer."""
+    who = "gae"
+    for name, x in (("reward", reward), ("done", done), ("value", value), ("last_value", last_value)):
+        if x is None:
+            raise ValueError("%s: %s is None" % (who, name))
+    T = None if n_steps is None else int(n_steps)
+    for name, x in (("reward", reward), ("done", done), ("value", value), ("term_value", term_value), ("adv", adv), ("ret", ret)):
+        if x is not None and hasattr(x, "data_ptr") and len(x.shape) == 2:
+            if T is None:
+                T = int(x.shape[0])
+            elif int(x.shape[0]) != T:
+                raise ValueError("%s: the %s tape holds %d steps, the others T = %d" % (who, name, int(x.shape[0]), T))
+    if T is None:
+        raise ValueError("%s: raw pointers need n_steps" % who)
+    if T < 1:
+        raise ValueError("%s: T must be >= 1, not %d" % (who, T))
+    for name, x, dtype in (("reward", reward, "float32"), ("done", done, "uint8"), ("value", value, "float32"),
+                           ("term_value", term_value, "float32"), ("adv", adv, "float32"), ("ret", ret, "float32")):
+        if x is not None:
+            _check_device_buffer(who, name, x, (T, n), dtype)
+    _check_device_buffer(who, "last_value", last_value, (n,), "float32")
+    out = []
+    for name, g in (("gamma", gamma), ("lam", lam)):
+        if isinstance(g, bool) or not isinstance(g, (int, float, np.integer, np.floating)):
+            raise ValueError("%s: %s must be a number, not %s" % (who, name, type(g).__name__))
+        g = float(g)
+        if not (0.0 <= g <= 1.0):
+            raise ValueError("%s: %s must be in [0, 1], not %r" % (who, name, g))
+        out.append(g)
+    return T, out[0], out[1]
+
+
+class ObsNorm:
+    """The running observation normaliser of :meth:`HipBatch.set_policy_obs_norm`: owns the two float32 device tensors ``mean`` and
+    ``inv_std`` [nobs] that the policy kernels read in place, and the float64 running count / mean / M2 behind them.
+    :meth:`update` merges the moments of a chunk of observations and rewrites both tensors in place; :meth:`normalize` is the expression
+    the kernel evaluates, so ``pi(norm.normalize(prev))`` sees bit for bit the inputs the recorded actions were computed from."""
+
+    def __init__(self, nobs, device, clip=10.0, eps=1e-8):
+        import torch
+        self.nobs, self.clip, self.eps = int(nobs), float(clip), float(eps)
+        if not np.isfinite(self.clip) or self.clip < 0:
+            raise ValueError("ObsNorm: clip must be finite and >= 0 (0: no clamp), not %r" % self.clip)
+        if not np.isfinite(self.eps) or self.eps < 0:
+            raise ValueError("ObsNorm: eps must be finite and >= 0, not %r" % self.eps)
+        self.mean = torch.zeros(self.nobs, dtype=torch.float32, device=device)
+        self.inv_std = torch.ones(self.nobs, dtype=torch.float32, device=device)
+        self.count = 0
+        self.mean64 = torch.zeros(self.nobs, dtype=torch.float64, device=device)
+        self.m2 = torch.zeros(self.nobs, dtype=torch.float64, device=device)
+
+    def update(self, obs):
+        """Merge the moments of ``obs`` [..., nobs] (Chan's parallel merge, float64) and rewrite ``mean`` / ``inv_std`` in place."""
+        import torch
+        if int(obs.shape[-1]) != self.nobs:
+            raise ValueError("ObsNorm.update: the last dimension must be nobs = %d, not %d" % (self.nobs, int(obs.shape[-1])))
+        x = obs.detach().reshape(-1, self.nobs).to(device=self.mean64.device, dtype=torch.float64)
+        m = int(x.shape[0])
+        if m == 0:
+            return
+        var, mean = torch.var_mean(x, dim=0, unbiased=False)
+        total = self.count + m
+        delta = mean - self.mean64
+        self.mean64 += delta * (m / total)
+        self.m2 += var * m + delta * delta * (self.count * m / total)
+        self.count = total
+        self.mean.copy_(self.mean64)
+        self.inv_std.copy_(1.0 / torch.sqrt(self.m2 / total + self.eps))
+
+    def normalize(self, x):
+        y = (x - self.mean) * self.inv_std
+        return y.clamp(-self.clip, self.clip) if self.clip > 0 else y
+
+
+SNAPSHOT_BLOB_HEADER = 64         # bytes in front of the payload of lm_snapshot_export (include/locohip.h)
 
 
 def check_restore_args(n, src=None, mask=None, snapshot=None, batch=None):
@@ -521,6 +636,7 @@ class HipBatch:
         self.na = d.na
         self._term_on, self._term_out = False, None              # terminal observations: enabled; a caller's tensor, kept alive
         self._pinned = self._pinned_term = None                  # views of the pinned ring (step_pinned)
+        self._obs_norm = None                                    # the policy's input normalisation: the caller's tensors, kept alive
         self._compiler_on, self.n_variants, self.n_model_draws, self._table_sizes = False, 0, 0, None
 
     def close(self):
@@ -532,6 +648,7 @@ class HipBatch:
             self._h = None
         self._term_out = None              # a caller's terminal-observation tensor, the pinned ring's views
         self._pinned = self._pinned_term = None
+        self._obs_norm = None
 
     __del__ = close
 
@@ -851,6 +968,36 @@ class HipBatch:
                                            _stream_ptr(stream), int(bool(sync)), C.byref(st) if sync else None))
         self.last_policy_stats = st.as_dict() if sync else None
         return actions
+
+    def set_policy_obs_norm(self, mean=None, inv_std=None, clip=0.0):
+        """Input normalisation of the policy of :meth:`rollout_policy` (``lm_set_policy_obs_norm``): the MLP reads
+        ``((obs - mean) * inv_std).clamp(-clip, clip)`` (``clip`` 0: no clamp) in place of the raw observation row. ``mean`` /
+        ``inv_std``: float32 device tensors [nobs] in the kernel's column order, read in place at every evaluation — an in-place update
+        (:meth:`ObsNorm.update`) is seen by the next call; the batch keeps references to them. Both None: off (the default). The
+        observation, terminal and action tapes are not affected: only what the policy reads. A setting, not part of a snapshot."""
+        clip = check_obs_norm_args(self.nobs, mean, inv_std, clip)
+        _check(self._lib.lm_set_policy_obs_norm(self._h, _dev_ptr(mean), _dev_ptr(inv_std), clip))
+        self._obs_norm = (mean, inv_std)
+
+    def gae(self, reward, done, value, last_value, term_value=None, gamma=0.99, lam=0.95, adv=None, ret=None, stream=None, sync=True,
+            n_steps=None):
+        """Generalised advantage estimation over the tapes of :meth:`rollout_tape` / :meth:`rollout_policy` in one launch
+        (``lm_tape_gae``), the done byte's bits told apart: no bootstrap at an absorbing state (``done & 1``), a bootstrap from
+        ``term_value[t, e]`` = V(terminal tape row) at a truncation (``done == 2``; None: 0), the trace cut at every restart.
+        ``reward`` / ``value`` float32 [T, n], ``done`` uint8 [T, n], ``last_value`` float32 [n] = V(obs[T-1]); ``value[t]`` = V of the
+        observation step t's action was computed from (obs0, then obs[t-1]). ``adv`` / ``ret`` float32 [T, n] are allocated with torch
+        when not given. ``stream`` / ``sync`` as in :meth:`rollout_tape`: queued behind the rollout that fills the tapes. Returns
+        ``(adv, ret)``."""
+        T, gamma, lam = check_gae_args(self.n, reward, done, value, last_value, term_value, gamma, lam, adv, ret, n_steps)
+        if adv is None or ret is None:
+            import torch
+            if not hasattr(value, "device"):
+                raise ValueError("gae: adv and ret can only be allocated beside a value tensor; pass both with raw pointers")
+            adv = torch.empty((T, self.n), dtype=torch.float32, device=value.device) if adv is None else adv
+            ret = torch.empty((T, self.n), dtype=torch.float32, device=value.device) if ret is None else ret
+        _check(self._lib.lm_tape_gae(self._h, T, _dev_ptr(reward), _dev_ptr(done), _dev_ptr(value), _dev_ptr(last_value), _dev_ptr(term_value),
+                                     gamma, lam, _dev_ptr(adv), _dev_ptr(ret), _stream_ptr(stream), int(bool(sync))))
+        return adv, ret
 
     # ---- snapshots (include/locohip.h lm_snapshot_*)
     def snapshot_signature(self):

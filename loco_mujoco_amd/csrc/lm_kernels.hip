@@ -82,6 +82,9 @@ struct lm_batch {
   // that collect no terminal observations, the sink [N][nobs] the policy kernels' terminal store writes to (they are compiled with
   // that store only). Scratch of a launch, allocated by the first policy call: nothing of it is state, nothing enters a snapshot
   float *pol_hand, *pol_sink;
+  // the policy's input normalisation (lm_set_policy_obs_norm): the caller's device tensors, read in place by every policy evaluation; mean
+  // null: off. A setting like the terminal-observation buffer: not state, not in a snapshot
+  lmp::PolicyNorm pol_norm;
   // every device or pinned array above that the batch owns: its field's address, entered by batch_array where the array is allocated.
   // lm_batch_destroy releases what these fields hold at that moment and names none of them
   struct Owned { void** field; bool pinned; };
@@ -92,6 +95,7 @@ namespace lmp {
 // step that runs as a launch of its own; the step kernel then reads the action row in action_mode 0, on the same stream.
 struct PolicyArgs {
   lm_mlp_policy p;
+  PolicyNorm norm;           // the input normalisation (lm_set_policy_obs_norm; mean null: off)
   const float* obs;          // [N][nobs]: the observation the action is computed from
   float* act;                // [N][nu]: this control step's row of the action tape
   const int* env_map; int n_active;      // the active list (lm_step.h KArgs): slot -> environment, or null
@@ -105,7 +109,7 @@ __global__ __launch_bounds__(64) void policy_kernel(PolicyArgs a) {
   if (slot >= a.n_active) return;           // (nothing below joins the whole workgroup)
   const int e = a.env_map ? a.env_map[slot] : slot;
   const int nobs = a.p.sizes[0], nu = a.p.sizes[a.p.n_layers];
-  policy_row(a.p, a.obs + (long long)e * nobs, a.act + (long long)e * nu, hand[e_local], lane, a.noise_seed, a.env_offset + e, a.step_index);
+  policy_row(a.p, a.norm, a.obs + (long long)e * nobs, a.act + (long long)e * nu, hand[e_local], lane, a.noise_seed, a.env_offset + e, a.step_index);
 }
 
 static void launch_policy(const PolicyArgs& a, hipStream_t stream) {
@@ -936,11 +940,11 @@ static int queue_steps(lm_batch* b, hipStream_t stream, const StepIO& io, int n_
       const float* prev = s == 0 ? pol->obs0 : io.obs + (s - 1) * io.obs_stride;
       a.pol.d_params = nullptr;
       if (a.nfused > 1) {
-        a.pol = pol->p; a.pol_obs0 = prev; a.pol_seed = pol->noise_seed; a.pol_hand = b->pol_hand;
+        a.pol = pol->p; a.pol_obs0 = prev; a.pol_seed = pol->noise_seed; a.pol_hand = b->pol_hand; a.pol_norm = b->pol_norm;
         if (!a.term_obs) a.term_obs = b->pol_sink;
       } else {
         if (!io.term) a.term_obs = b->term_obs;        // (not the sink of an earlier fused launch of this call)
-        lmp::PolicyArgs pa = {pol->p, prev, const_cast<float*>(a.action), b->env_map, b->n_active, pol->noise_seed, b->env_offset, b->step_index};
+        lmp::PolicyArgs pa = {pol->p, b->pol_norm, prev, const_cast<float*>(a.action), b->env_map, b->n_active, pol->noise_seed, b->env_offset, b->step_index};
         lmp::launch_policy(pa, stream);
       }
     }
@@ -1083,6 +1087,19 @@ int lm_set_terminal_obs(lm_batch* b, int enabled, float* d_out) {
   HIPCHK(hipMemsetAsync(b->term_own, 0, bytes, b->stream));
   HIPCHK(hipStreamSynchronize(b->stream));
   b->term_obs = b->term_own;
+  return 0;
+}
+
+int lm_set_policy_obs_norm(lm_batch* b, const float* d_mean, const float* d_inv_std, float clip) {
+  if (!b) return fail("null batch");
+  // every argument is checked before anything changes: a refused call leaves the setting as it was
+  if ((d_mean == nullptr) != (d_inv_std == nullptr)) return fail("lm_set_policy_obs_norm: d_mean and d_inv_std go together (both NULL: off)");
+  if (!std::isfinite(clip) || clip < 0.0f) return fail("lm_set_policy_obs_norm: clip must be finite and >= 0 (0: no clamp)");
+  HIPCHK(hipSetDevice(b->m->device));
+  // no launch in flight still reads the tensors that are being replaced (as lm_set_terminal_obs: the library's stream is ordered behind
+  // every launch on a caller's stream). Like d_params the pointers are taken as given: [nobs] float32 on the batch's device
+  HIPCHK(hipStreamSynchronize(b->stream));
+  b->pol_norm.mean = d_mean; b->pol_norm.inv_std = d_inv_std; b->pol_norm.clip = d_mean ? clip : 0.0f;
   return 0;
 }
 
@@ -1268,6 +1285,65 @@ int lm_rollout_policy(lm_batch* b, const lm_mlp_policy* p, int n_steps, int step
     if (drain_stats(b)) return 1;
     *stats = b->acc; stats->kernel_ms = ms;
   }
+  return 0;
+}
+
+// Generalised advantage estimation over the tapes (locohip.h lm_tape_gae): one environment per lane, so that every row [t][.] of a tape
+// is read and written coalesced; t runs from T-1 down with adv[t+1] and V[t+1] kept in registers. No step kernel: no LDS, no family.
+// Every line is spelled out in single operations and explicit fmaf calls (-ffp-contract has nothing to decide), and what a cut makes
+// unreachable is chosen away by selects, never multiplied by a mask: a NaN there does not reach the output.
+namespace lmg {
+struct GaeArgs {
+  const float *reward, *value, *last_value, *term_value; const unsigned char* done;
+  float gamma, lam; float *adv, *ret; int T; long long N;
+};
+constexpr int kGaeBlock = 256;
+
+__global__ __launch_bounds__(kGaeBlock) void gae_kernel(GaeArgs a) {
+  const long long e = (long long)blockIdx.x * kGaeBlock + threadIdx.x;
+  if (e >= a.N) return;
+  const float gl = a.gamma * a.lam;
+  float adv_next = 0.0f, v_next = 0.0f;
+  for (int t = a.T - 1; t >= 0; t--) {
+    const long long at = (long long)t * a.N + e;
+    const unsigned char d = a.done[at];
+    const bool last = t == a.T - 1;
+    const float r = a.reward[at], v = a.value[at];
+    float next_v;
+    if (d & 1) next_v = 0.0f;
+    else if (d & 2) next_v = a.term_value ? a.term_value[at] : 0.0f;
+    else next_v = last ? a.last_value[e] : v_next;
+    const float delta = fmaf(a.gamma, next_v, r) - v;
+    const float adv = (d != 0 || last) ? delta : fmaf(gl, adv_next, delta);
+    if (a.adv) a.adv[at] = adv;
+    if (a.ret) a.ret[at] = adv + v;
+    adv_next = adv; v_next = v;
+  }
+}
+}  // namespace lmg
+
+int lm_tape_gae(lm_batch* b, int n_steps, const float* d_reward, const uint8_t* d_done, const float* d_value, const float* d_last_value,
+                const float* d_term_value, float gamma, float lam, float* d_adv, float* d_ret, void* stream, int sync) {
+  if (!b) return fail("null batch");
+  // every argument is checked before the launch: a refused call launches nothing
+  if (n_steps < 1) return fail("lm_tape_gae: n_steps must be >= 1");
+  if (!d_reward) return fail("lm_tape_gae: d_reward is null");
+  if (!d_done) return fail("lm_tape_gae: d_done is null");
+  if (!d_value) return fail("lm_tape_gae: d_value is null");
+  if (!d_last_value) return fail("lm_tape_gae: d_last_value is null");
+  if (!d_adv && !d_ret) return fail("lm_tape_gae: d_adv and d_ret are both null (nothing to compute)");
+  if (!(gamma >= 0.0f && gamma <= 1.0f)) return fail("lm_tape_gae: gamma must be in [0, 1]");
+  if (!(lam >= 0.0f && lam <= 1.0f)) return fail("lm_tape_gae: lam must be in [0, 1]");
+  HIPCHK(hipSetDevice(b->m->device));
+  const lmg::GaeArgs a = {d_reward, d_value, d_last_value, d_term_value, d_done, gamma, lam, d_adv, d_ret, n_steps, (long long)b->N};
+  // on the given stream behind everything the batch has in flight (the rollout that fills the tapes), as the snapshot copy is
+  StreamScope scope(b, stream);
+  if (scope.enter()) return 1;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(lmg::gae_kernel, dim3((unsigned)((a.N + lmg::kGaeBlock - 1) / lmg::kGaeBlock)), dim3(lmg::kGaeBlock), 0, scope.used, a);
+  HIPCHK(hipGetLastError());
+  if (scope.leave()) return 1;
+  if (sync) HIPCHK(hipStreamSynchronize(scope.used));
   return 0;
 }
 

@@ -74,6 +74,14 @@ __device__ __forceinline__ void policy_units(const float* __restrict__ W, const 
   }
 }
 
+// INPUT NORMALISATION (locohip.h lm_set_policy_obs_norm): what the first layer reads is clamp((obs - mean) * inv_std, -clip, clip), the
+// running standardiser in front of a locomotion actor. mean / inv_std: the caller's device tensors [nobs] in the kernel's column order,
+// read in place at every evaluation like the parameters; mean null: off — the load below is then the plain copy it was. One subtraction,
+// one multiplication and two selects, each a single rounding of its own (nothing here can contract; the product is made opaque all the
+// same, so that the selects stay selects whatever surrounds the call): torch's ((x - mean) * inv_std).clamp(-clip, clip) bit for bit,
+// a NaN staying NaN. clip == 0: no clamp. Only the policy's input is normalised: the observation row itself stays as the step wrote it.
+struct PolicyNorm { const float* mean; const float* inv_std; float clip; };
+
 template <bool GLOBAL_HAND>
 __device__ __forceinline__ void policy_handover() {
   if (GLOBAL_HAND) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
@@ -85,10 +93,19 @@ __device__ __forceinline__ void policy_handover() {
 // hand-over buffer [2][kPolicyMaxWidth] of this environment. gid = the GLOBAL environment id, step = the batch's count of control
 // steps at this step: with p.d_log_std the key of the noise (noise_seed, gid, step, k).
 template <bool GLOBAL_HAND = false>
-__device__ __forceinline__ void policy_row(const lm_mlp_policy& p, const float* __restrict__ obs, float* __restrict__ act, float* h, int lane,
+__device__ __forceinline__ void policy_row(const lm_mlp_policy& p, const PolicyNorm& nrm, const float* __restrict__ obs, float* __restrict__ act, float* h, int lane,
                                            unsigned long long noise_seed, long long gid, unsigned step) {
   float* x = h; float* y = h + kPolicyMaxWidth;
-  for (int i = lane; i < p.sizes[0]; i += 16) x[i] = obs[i];
+  if (nrm.mean) {
+    const float clip = nrm.clip;
+    for (int i = lane; i < p.sizes[0]; i += 16) {
+      const float d = policy_opaque(obs[i] - nrm.mean[i]);
+      const float t = policy_opaque(d * nrm.inv_std[i]);
+      x[i] = clip > 0.0f ? (t < -clip ? -clip : (t > clip ? clip : t)) : t;
+    }
+  } else {
+    for (int i = lane; i < p.sizes[0]; i += 16) x[i] = obs[i];
+  }
   policy_handover<GLOBAL_HAND>();
   const float* prm = p.d_params;
   for (int l = 0; l < p.n_layers; l++) {

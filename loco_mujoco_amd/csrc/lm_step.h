@@ -209,6 +209,9 @@ struct KArgs {
   // the step before stored (obs + (fused - 1) * tape_obs) and write row `fused` of the action tape, which the step then reads as any
   // tape action. pol_hand: [N][2 * lmp::kPolicyMaxWidth] floats, the lanes' hand-over of hidden activations (scratch of a launch).
   lm_mlp_policy pol; const float* pol_obs0; unsigned long long pol_seed; float* pol_hand;
+  // the policy's input normalisation (lm_set_policy_obs_norm, lm_policy.h PolicyNorm; mean null: off). Read where `pol` is and nowhere
+  // else, and behind it for the same reason
+  lmp::PolicyNorm pol_norm;
 };
 
 __device__ __forceinline__ unsigned long long mix64(unsigned long long x) {
@@ -378,7 +381,7 @@ __global__ __launch_bounds__(64) void step_kernel(KArgs a) {
     if (in_range && !gone && (!REPLAY || fused > first_step)) {
       const float* prev = (fused == 0 ? a.pol_obs0 : a.obs + (fused - 1) * a.tape_obs) + (long long)e * a.T.nobs;
       float* row = const_cast<float*>(a.action) + fused * a.tape_action + (long long)e * a.T.nu;
-      lmp::policy_row<true>(a.pol, prev, row, a.pol_hand + (long long)e * (2 * lmp::kPolicyMaxWidth), (int)(threadIdx.x & 15), a.pol_seed, a.env_offset + e, step_index);
+      lmp::policy_row<true>(a.pol, a.pol_norm, prev, row, a.pol_hand + (long long)e * (2 * lmp::kPolicyMaxWidth), (int)(threadIdx.x & 15), a.pol_seed, a.env_offset + e, step_index);
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");      // the row is read by lanes that did not write it
   }

@@ -2,6 +2,9 @@
   (a) rollout_policy, 25 control steps per launch (the policy inside the fused kernel),
   (b) rollout_policy, 1 control step per launch (policy_kernel + the ordinary step kernel),
   (c) the same torch module driving step_device in a loop on one stream (a handful of torch launches + one step launch per step),
+  (d) as (a) with the input normaliser on (set_policy_obs_norm) at mean 0, inv_std 1 and a clip no input reaches: the subtraction, the
+      multiplication and the selects run, the actions stay bitwise those of (a) — a normaliser with real moments changes the actions, the
+      states the robots get into and with them the cost of the STEP, for every leg that shares the batch,
 for UnitreeA1.simple and HumanoidTorque.run. Device-side restarts at the task's horizon, 50 warm-up steps, then `steps` control steps
 per repeat timed by HIP events on the caller's stream, `repeats` repeats per leg, the legs alternating. Noise on (log_std = -1): (c)
 draws its own normal numbers with torch. Usage: policy_rollout_time.py [steps] [repeats] [n_envs]"""
@@ -13,7 +16,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from loco_mujoco_amd import LocoEnv  # noqa: E402
-from loco_mujoco_amd.backend import MlpPolicy  # noqa: E402
+from loco_mujoco_amd.backend import MlpPolicy, ObsNorm  # noqa: E402
 
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 500
 repeats = int(sys.argv[2]) if len(sys.argv) > 2 else 3
@@ -56,20 +59,37 @@ for task in ("UnitreeA1.simple", "HumanoidTorque.run"):
         if (count % K) != 0:
             obs[K - 1].copy_(o)
 
+    norm = ObsNorm(b.nobs, dev, clip=3.0e38)              # never updated: mean 0, inv_std 1
+
+    def leg_normalised(count):
+        leg_fused(count, K)
+
     legs = (("(a) rollout_policy, 25 steps per launch", lambda c: leg_fused(c, K)), ("(b) rollout_policy, 1 step per launch", lambda c: leg_fused(c, 1)),
-            ("(c) torch module + step_device loop", leg_loop))
+            ("(c) torch module + step_device loop", leg_loop), ("(d) as (a), input normaliser on", leg_normalised))
+
+    def prepare(leg):
+        # the setting waits for the batch's launches on the host: outside the timed span
+        if leg is leg_normalised:
+            b.set_policy_obs_norm(norm.mean, norm.inv_std, norm.clip)
+        else:
+            b.set_policy_obs_norm(None, None)
+
     times = {name: [] for name, _ in legs}
     for name, leg in legs:
+        prepare(leg)
         leg(50)
     torch.cuda.synchronize(dev)
     for _ in range(repeats):
         for name, leg in legs:
+            prepare(leg)
+            torch.cuda.synchronize(dev)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(stream)
             leg(steps)
             e1.record(stream)
             e1.synchronize()
             times[name].append(e0.elapsed_time(e1) / steps)
+    b.set_policy_obs_norm(None, None)
     for name, _ in legs:
         t = sorted(times[name])
         print("%s n=%d %s: ms per control step %s, median %.4f, spread %.4f" % (task, n, name, ", ".join("%.4f" % v for v in times[name]),
