@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("LOCOHIP_LIB", os.path.join(_HERE, "csrc", "liblocohip
 _F = C.POINTER(C.c_float)
 _U8 = C.POINTER(C.c_uint8)
 _D = C.POINTER(C.c_double)
+_I32 = C.POINTER(C.c_int32)
 
 
 class Dims(C.Structure):
@@ -39,16 +40,41 @@ class ForwardOut(C.Structure):
                [("ncon", C.POINTER(C.c_int)), ("solver_iter", C.POINTER(C.c_int))]
 
 
-EXPORTS = ["lm_device_count", "lm_last_error", "lm_toolchain", "lm_lds_bytes", "lm_model_create", "lm_model_destroy", "lm_model_dims",
-           "lm_batch_create", "lm_batch_destroy", "lm_batch_set_layout", "lm_batch_set_replay", "lm_batch_set_active", "lm_get_replay_marks", "lm_set_state", "lm_get_state", "lm_set_activation", "lm_get_activation",
-           "lm_set_dof_params", "lm_get_dof_params", "lm_set_dof_randomization", "lm_set_goal", "lm_step", "lm_step_device",
-           "lm_pinned_slot", "lm_set_obs_order", "lm_step_pinned",
-           "lm_set_terminal_obs", "lm_get_terminal_obs", "lm_pinned_terminal_obs",
-           "lm_set_reset_table", "lm_set_auto_reset", "lm_rollout", "lm_rollout_fused", "lm_rollout_tape", "lm_rollout_policy", "lm_set_policy_obs_norm", "lm_tape_gae", "lm_forward_debug", "lm_get_stats", "lm_sync",
-           "lm_get_flags", "lm_set_model_variants", "lm_set_variant_index", "lm_get_variant_index", "lm_set_variant_rows",
-           "lm_set_model_compiler", "lm_compile_models", "lm_get_model_draws", "lm_get_model_tables",
-           "lm_snapshot_create", "lm_snapshot_destroy", "lm_snapshot_save", "lm_snapshot_restore", "lm_snapshot_bytes",
-           "lm_snapshot_export", "lm_snapshot_import"]
+# THE prototypes of include/locohip.h, stated once: name -> (restype, argtypes). load_library() declares every one of them and EXPORTS
+# is the key list, so an export cannot be listed and left to ctypes' default conversions. argtypes None: the function takes no argument
+_P, _I, _LL, _U64, _FL, _ST = C.c_void_p, C.c_int, C.c_longlong, C.c_uint64, C.c_float, C.POINTER(Stats)
+_PROTOTYPES = {
+    "lm_device_count": (_I, None), "lm_last_error": (C.c_char_p, None), "lm_toolchain": (C.c_char_p, None),
+    "lm_lds_bytes": (_I, [_I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I)]),
+    "lm_model_create": (_I, [_D, C.c_size_t, _I, C.POINTER(_P)]), "lm_model_destroy": (None, [_P]), "lm_model_dims": (_I, [_P, C.POINTER(Dims)]),
+    "lm_batch_create": (_I, [_P, _I, C.POINTER(_P)]), "lm_batch_destroy": (None, [_P]),
+    "lm_batch_set_layout": (_I, [_P, _I]), "lm_batch_set_replay": (_I, [_P, _I]), "lm_batch_set_active": (_I, [_P, _I32, _I]),
+    "lm_get_replay_marks": (_I, [_P, _U8, _I]),
+    "lm_set_state": (_I, [_P, _F, _F, _U8]), "lm_get_state": (_I, [_P, _F, _F]),
+    "lm_set_activation": (_I, [_P, _F, _U8]), "lm_get_activation": (_I, [_P, _F]),
+    "lm_set_dof_params": (_I, [_P, _F, _F, _F, _U8]), "lm_get_dof_params": (_I, [_P, _F, _F, _F]), "lm_set_dof_randomization": (_I, [_P, _F]),
+    "lm_set_goal": (_I, [_P, _F, _U8]),
+    "lm_step": (_I, [_P, _F, _F, _F, _U8]), "lm_step_device": (_I, [_P, _P, _P, _P, _P, _P, _I]),
+    "lm_pinned_slot": (_I, [_P, _I, C.POINTER(_D), C.POINTER(_D), C.POINTER(_U8)]), "lm_set_obs_order": (_I, [_P, _I32, _I]),
+    "lm_step_pinned": (_I, [_P, _D, _I]),
+    "lm_set_terminal_obs": (_I, [_P, _I, _P]), "lm_get_terminal_obs": (_I, [_P, _F]), "lm_pinned_terminal_obs": (_I, [_P, _I, C.POINTER(_D)]),
+    "lm_set_reset_table": (_I, [_P, _F, _I, _U64, C.c_int64]), "lm_set_auto_reset": (_I, [_P, _I, _I]),
+    "lm_rollout": (_I, [_P, _I, _I, _U64, _ST]), "lm_rollout_fused": (_I, [_P, _I, _I, _I, _U64, _ST]),
+    "lm_rollout_tape": (_I, [_P, _I, _I, _P, _LL, _P, _P, _P, _P, _P, _I, _ST]),
+    "lm_rollout_policy": (_I, [_P, C.POINTER(MlpPolicyStruct), _I, _I, _U64, _P, _P, _P, _P, _P, _P, _P, _I, _ST]),
+    "lm_set_policy_obs_norm": (_I, [_P, _P, _P, _FL]),
+    "lm_tape_gae": (_I, [_P, _I, _P, _P, _P, _P, _P, _FL, _FL, _P, _P, _P, _I]),
+    "lm_forward_debug": (_I, [_P, _F, C.POINTER(ForwardOut)]), "lm_get_stats": (_I, [_P, _ST, _I]), "lm_sync": (_I, [_P]),
+    "lm_get_flags": (_I, [_P, _U8]),
+    "lm_set_model_variants": (_I, [_P, _F, _F, _F, _I, _I]), "lm_set_variant_index": (_I, [_P, _I32, _U8]),
+    "lm_get_variant_index": (_I, [_P, _I32]), "lm_set_variant_rows": (_I, [_P, _I]),
+    "lm_set_model_compiler": (_I, [_P, _I32, _LL, _D, _LL, _F, _F, _F, _I, _U64]), "lm_compile_models": (_I, [_P, _U8]),
+    "lm_get_model_draws": (_I, [_P, _D, C.POINTER(C.c_uint32)]), "lm_get_model_tables": (_I, [_P, _I, _F, _F, _F]),
+    "lm_snapshot_create": (_I, [_P, _I, C.POINTER(_P)]), "lm_snapshot_destroy": (None, [_P]),
+    "lm_snapshot_save": (_I, [_P, _P, _P, _I]), "lm_snapshot_restore": (_I, [_P, _P, _P, _P, _I]), "lm_snapshot_bytes": (_LL, [_P]),
+    "lm_snapshot_export": (_I, [_P, _P, _P, _LL]), "lm_snapshot_import": (_I, [_P, _P, _P, _LL]),
+}
+EXPORTS = list(_PROTOTYPES)
 
 _lib = None
 
@@ -66,70 +92,11 @@ def load_library():
         raise BackendError("HIP library not built: %s is missing (run `python -c 'import __graft_entry__ as g; "
                            "g.build()'` or `make -C loco_mujoco_amd/csrc`). There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    lib.lm_device_count.restype = C.c_int
-    lib.lm_last_error.restype = C.c_char_p
-    lib.lm_toolchain.restype = C.c_char_p
-    lib.lm_lds_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    lib.lm_model_create.argtypes = [_D, C.c_size_t, C.c_int, C.POINTER(C.c_void_p)]
-    lib.lm_model_destroy.argtypes = [C.c_void_p]
-    lib.lm_model_destroy.restype = None
-    lib.lm_model_dims.argtypes = [C.c_void_p, C.POINTER(Dims)]
-    lib.lm_batch_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
-    lib.lm_batch_set_layout.argtypes = [C.c_void_p, C.c_int]
-    lib.lm_batch_set_replay.argtypes = [C.c_void_p, C.c_int]
-    lib.lm_batch_set_active.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int]
-    lib.lm_get_replay_marks.argtypes = [C.c_void_p, _U8, C.c_int]
-    lib.lm_batch_destroy.argtypes = [C.c_void_p]
-    lib.lm_batch_destroy.restype = None
-    lib.lm_set_state.argtypes = [C.c_void_p, _F, _F, _U8]
-    lib.lm_get_state.argtypes = [C.c_void_p, _F, _F]
-    lib.lm_set_goal.argtypes = [C.c_void_p, _F, _U8]
-    lib.lm_set_dof_params.argtypes = [C.c_void_p, _F, _F, _F, _U8]
-    lib.lm_get_dof_params.argtypes = [C.c_void_p, _F, _F, _F]
-    lib.lm_set_dof_randomization.argtypes = [C.c_void_p, _F]
-    lib.lm_step_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-    lib.lm_set_activation.argtypes = [C.c_void_p, _F, _U8]
-    lib.lm_get_activation.argtypes = [C.c_void_p, _F]
-    lib.lm_step.argtypes = [C.c_void_p, _F, _F, _F, _U8]
-    lib.lm_pinned_slot.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.POINTER(C.c_double)), C.POINTER(_U8)]
-    lib.lm_set_obs_order.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int]
-    lib.lm_step_pinned.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int]
-    lib.lm_set_terminal_obs.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    lib.lm_get_terminal_obs.argtypes = [C.c_void_p, _F]
-    lib.lm_pinned_terminal_obs.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.POINTER(C.c_double))]
-    lib.lm_set_reset_table.argtypes = [C.c_void_p, _F, C.c_int, C.c_uint64, C.c_int64]
-    lib.lm_set_auto_reset.argtypes = [C.c_void_p, C.c_int, C.c_int]
-    lib.lm_rollout.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.POINTER(Stats)]
-    lib.lm_rollout_fused.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(Stats)]
-    lib.lm_rollout_tape.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_void_p, C.c_int, C.POINTER(Stats)]
-    lib.lm_rollout_policy.argtypes = [C.c_void_p, C.POINTER(MlpPolicyStruct), C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(Stats)]
-    lib.lm_set_policy_obs_norm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float]
-    lib.lm_tape_gae.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
-                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-    lib.lm_forward_debug.argtypes = [C.c_void_p, _F, C.POINTER(ForwardOut)]
-    lib.lm_get_stats.argtypes = [C.c_void_p, C.POINTER(Stats), C.c_int]
-    lib.lm_sync.argtypes = [C.c_void_p]
-    lib.lm_get_flags.argtypes = [C.c_void_p, _U8]
-    lib.lm_set_model_variants.argtypes = [C.c_void_p, _F, _F, _F, C.c_int, C.c_int]
-    lib.lm_set_variant_index.argtypes = [C.c_void_p, C.POINTER(C.c_int32), _U8]
-    lib.lm_get_variant_index.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
-    lib.lm_set_variant_rows.argtypes = [C.c_void_p, C.c_int]
-    lib.lm_set_model_compiler.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_longlong, C.POINTER(C.c_double), C.c_longlong, _F, _F, _F,
-                                          C.c_int, C.c_uint64]
-    lib.lm_compile_models.argtypes = [C.c_void_p, _U8]
-    lib.lm_get_model_draws.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
-    lib.lm_get_model_tables.argtypes = [C.c_void_p, C.c_int, _F, _F, _F]
-    lib.lm_snapshot_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
-    lib.lm_snapshot_destroy.argtypes = [C.c_void_p]
-    lib.lm_snapshot_destroy.restype = None
-    lib.lm_snapshot_save.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-    lib.lm_snapshot_restore.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-    lib.lm_snapshot_bytes.argtypes = [C.c_void_p]
-    lib.lm_snapshot_bytes.restype = C.c_longlong
-    lib.lm_snapshot_export.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong]
-    lib.lm_snapshot_import.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong]
+    for name, (restype, argtypes) in _PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype = restype          # (c_int is also what ctypes assumes)
+        if argtypes is not None:
+            fn.argtypes = argtypes
     _lib = lib
     return lib
 
@@ -146,15 +113,58 @@ def _f32(a, shape=None):
     return a
 
 
-def _fp(a):
-    return a.ctypes.data_as(_F)
+def _ptr(a, ctype=_F):
+    """A host array as the C pointer a prototype asks for."""
+    return a.ctypes.data_as(ctype)
 
 
 def _mask(mask, n):
     if mask is None:
         return None, None
     m = np.ascontiguousarray(mask, dtype=np.uint8).reshape(n)
-    return m, m.ctypes.data_as(_U8)
+    return m, _ptr(m, _U8)
+
+
+# THE device-buffer check's wording per fault; a caller whose messages read differently passes its own templates over the same values
+_BUFFER_FAULTS = {"pointer": "%(who)s: %(name)s must be a device tensor (data_ptr()) or a raw device pointer (int), not %(type)s",
+                  "shape": "%(who)s: %(name)s must be %(shape)s, not %(got)s",
+                  "dtype": "%(who)s: %(name)s must be %(dtype)s, not %(got)s",
+                  "contiguous": "%(who)s: %(name)s must be contiguous",
+                  "device": "%(who)s: %(name)s must live on the device"}
+
+
+def _check_device_buffer(who, name, x, shape, dtype, raw=True, faults=("shape", "dtype", "contiguous", "device"), say=None):
+    """``x``: a raw device pointer (int), taken as given (``raw`` False: refused), or a described object (torch tensor, anything with
+    ``shape`` / ``dtype`` / ``is_contiguous()`` / ``data_ptr()``): ``shape``, ``dtype``, contiguous, on the device, looked at in the order
+    of ``faults`` (empty: only that ``x`` is a buffer at all). ``say``: the caller's own wording of some faults (_BUFFER_FAULTS)."""
+    def refuse(fault, **found):
+        raise ValueError((say or {}).get(fault, _BUFFER_FAULTS[fault]) % dict(found, who=who, name=name, dtype=dtype))
+
+    if not hasattr(x, "data_ptr"):
+        if not raw or isinstance(x, bool) or not isinstance(x, (int, np.integer)):
+            refuse("pointer", type=type(x).__name__)
+        return
+    for fault in faults:
+        if fault == "shape" and tuple(x.shape) != tuple(shape):
+            refuse(fault, shape=list(shape), got=list(x.shape), got_tuple=tuple(x.shape))
+        if fault == "dtype" and dtype not in str(x.dtype):
+            refuse(fault, got=x.dtype)
+        if fault == "contiguous" and not x.is_contiguous():
+            refuse(fault)
+        if fault == "device" and hasattr(x, "is_cuda") and not x.is_cuda:
+            refuse(fault)
+
+
+def _number(who, name, v):
+    """``v`` as a float: a real number, not a bool."""
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise ValueError("%s: %s must be a number, not %s" % (who, name, type(v).__name__))
+    return float(v)
+
+
+def _tape_table(n, nobs):
+    """The tapes a rollout records, [T] in front of each: (name, shape of one step, dtype)."""
+    return (("obs", (n, nobs), "float32"), ("reward", (n,), "float32"), ("done", (n,), "uint8"), ("terminal", (n, nobs), "float32"))
 
 
 def check_tape_args(n, nu, nobs, actions, obs=None, reward=None, done=None, terminal=None, steps_per_launch=None, repeat=None,
@@ -162,36 +172,23 @@ def check_tape_args(n, nu, nobs, actions, obs=None, reward=None, done=None, term
     """The argument checks of :meth:`HipBatch.rollout_tape`, without a device: returns ``(T, action_step_stride, steps_per_launch)``
     or raises ValueError. Buffers are objects with ``shape`` / ``dtype`` / ``is_contiguous()`` / ``data_ptr()`` (torch tensors), which
     are checked, or raw device pointers (ints), which are taken as given and need ``n_steps`` (a tape) or ``repeat``."""
-    def described(x):
-        return hasattr(x, "data_ptr")
-
-    for name, x in (("actions", actions), ("obs", obs), ("reward", reward), ("done", done), ("terminal", terminal)):
-        if x is not None and not described(x) and (isinstance(x, bool) or not isinstance(x, (int, np.integer))):
-            raise ValueError("rollout_tape: %s must be a device tensor (data_ptr()) or a raw device pointer (int), not %s" % (name, type(x).__name__))
-
-    def check(name, x, shape, dtype):
-        if x is None or not described(x):
-            return
-        if tuple(x.shape) != tuple(shape):
-            raise ValueError("rollout_tape: %s must be %s, not %s" % (name, list(shape), list(x.shape)))
-        if dtype not in str(x.dtype):
-            raise ValueError("rollout_tape: %s must be %s, not %s" % (name, dtype, x.dtype))
-        if not x.is_contiguous():
-            raise ValueError("rollout_tape: %s must be contiguous" % name)
-        if hasattr(x, "is_cuda") and not x.is_cuda:
-            raise ValueError("rollout_tape: %s must live on the device" % name)
-
+    who = "rollout_tape"
+    given = dict(actions=actions, obs=obs, reward=reward, done=done, terminal=terminal)
+    for name, x in given.items():          # what is no buffer at all is refused before anything is said about any of them
+        if x is not None:
+            _check_device_buffer(who, name, x, None, None, faults=())
     if actions is None:
         raise ValueError("rollout_tape: actions is None (policy-free rollouts: rollout())")
+    described = hasattr(actions, "data_ptr")
     if repeat is not None:
         T, stride = int(repeat), 0
         if n_steps is not None and int(n_steps) != T:
             raise ValueError("rollout_tape: n_steps and repeat disagree")
-        if described(actions) and len(actions.shape) != 2:
+        if described and len(actions.shape) != 2:
             raise ValueError("rollout_tape: with repeat, actions must be [%d, %d], not %s" % (n, nu, list(actions.shape)))
-        check("actions", actions, (n, nu), "float32")
+        _check_device_buffer(who, "actions", actions, (n, nu), "float32")
     else:
-        if described(actions):
+        if described:
             if len(actions.shape) != 3:
                 raise ValueError("rollout_tape: actions must be [T, %d, %d] (or [%d, %d] with repeat=T), not %s" % (n, nu, n, nu, list(actions.shape)))
             T = int(actions.shape[0])
@@ -202,14 +199,16 @@ def check_tape_args(n, nu, nobs, actions, obs=None, reward=None, done=None, term
         else:
             T = int(n_steps)
         stride = n * nu
-        check("actions", actions, (T, n, nu), "float32")
+        _check_device_buffer(who, "actions", actions, (T, n, nu), "float32")
     if T < 1:
         raise ValueError("rollout_tape: T must be >= 1, not %d" % T)
-    for name, x, tail, dtype in (("obs", obs, (n, nobs), "float32"), ("reward", reward, (n,), "float32"), ("done", done, (n,), "uint8"),
-                                 ("terminal", terminal, (n, nobs), "float32")):
-        if x is not None and described(x) and len(x.shape) >= 1 and int(x.shape[0]) != T:
+    for name, step, dtype in _tape_table(n, nobs):
+        x = given[name]
+        if x is None:
+            continue
+        if hasattr(x, "data_ptr") and len(x.shape) >= 1 and int(x.shape[0]) != T:
             raise ValueError("rollout_tape: the %s tape holds %d steps, the actions T = %d" % (name, int(x.shape[0]), T))
-        check(name, x, (T,) + tail, dtype)
+        _check_device_buffer(who, name, x, (T,) + step, dtype)
     if terminal is not None and not terminal_enabled:
         raise ValueError("rollout_tape: a terminal tape needs terminal observations enabled (enable_terminal_obs)")
     spl = T if steps_per_launch is None else int(steps_per_launch)
@@ -223,17 +222,11 @@ POLICY_ACTIVATIONS = {"tanh": 0, "relu": 1}
 
 
 def _check_policy_tensor(name, x, count):
-    """``x``: an object with ``shape`` / ``dtype`` / ``is_contiguous()`` / ``data_ptr()``: float32, ``count`` elements, contiguous, on the device."""
-    if not hasattr(x, "data_ptr"):
-        raise ValueError("MlpPolicy: %s must be a device tensor (data_ptr()), not %s" % (name, type(x).__name__))
-    if "float32" not in str(x.dtype):
-        raise ValueError("MlpPolicy: %s must be float32, not %s" % (name, x.dtype))
-    if len(x.shape) != 1 or int(x.shape[0]) != count:
-        raise ValueError("MlpPolicy: %s must be a flat tensor of %d elements, not %s" % (name, count, list(x.shape)))
-    if not x.is_contiguous():
-        raise ValueError("MlpPolicy: %s must be contiguous" % name)
-    if hasattr(x, "is_cuda") and not x.is_cuda:
-        raise ValueError("MlpPolicy: %s must live on the device" % name)
+    """A tensor of :class:`MlpPolicy`: float32, ``count`` elements, contiguous, on the device, and no raw pointer (``struct()`` asks it for
+    its ``data_ptr()``). Its dtype is looked at before its shape, and its shape is worded as a count."""
+    _check_device_buffer("MlpPolicy", name, x, (count,), "float32", raw=False, faults=("dtype", "shape", "contiguous", "device"),
+                         say={"pointer": "%(who)s: %(name)s must be a device tensor (data_ptr()), not %(type)s",
+                              "shape": "%%(who)s: %%(name)s must be a flat tensor of %d elements, not %%(got)s" % count})
 
 
 class MlpPolicy:
@@ -337,6 +330,7 @@ def check_policy_args(n, nu, nobs, policy, n_steps, obs0=None, actions=None, obs
                       steps_per_launch=None, terminal_enabled=True):
     """The argument checks of :meth:`HipBatch.rollout_policy`, without a device: returns ``(T, steps_per_launch)`` or raises ValueError.
     Buffers are described objects (torch tensors), which are checked, or raw device pointers (ints), which are taken as given."""
+    who = "rollout_policy"
     if not isinstance(policy, MlpPolicy):
         raise ValueError("rollout_policy: policy must be an MlpPolicy, not %s" % type(policy).__name__)
     if policy.sizes[0] != nobs:
@@ -346,49 +340,17 @@ def check_policy_args(n, nu, nobs, policy, n_steps, obs0=None, actions=None, obs
     if isinstance(n_steps, bool) or not isinstance(n_steps, (int, np.integer)) or int(n_steps) < 1:
         raise ValueError("rollout_policy: n_steps must be an integer >= 1, not %r" % (n_steps,))
     T = int(n_steps)
-
-    def described(x):
-        return hasattr(x, "data_ptr")
-
-    for name, x, shape, dtype in (("obs0", obs0, (n, nobs), "float32"), ("actions", actions, (T, n, nu), "float32"),
-                                  ("obs", obs, (T, n, nobs), "float32"), ("reward", reward, (T, n), "float32"), ("done", done, (T, n), "uint8"),
-                                  ("terminal", terminal, (T, n, nobs), "float32")):
-        if x is None:
-            continue
-        if not described(x):
-            if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
-                raise ValueError("rollout_policy: %s must be a device tensor (data_ptr()) or a raw device pointer (int), not %s" % (name, type(x).__name__))
-            continue
-        if tuple(x.shape) != tuple(shape):
-            raise ValueError("rollout_policy: %s must be %s, not %s" % (name, list(shape), list(x.shape)))
-        if dtype not in str(x.dtype):
-            raise ValueError("rollout_policy: %s must be %s, not %s" % (name, dtype, x.dtype))
-        if not x.is_contiguous():
-            raise ValueError("rollout_policy: %s must be contiguous" % name)
-        if hasattr(x, "is_cuda") and not x.is_cuda:
-            raise ValueError("rollout_policy: %s must live on the device" % name)
+    given = dict(obs=obs, reward=reward, done=done, terminal=terminal)
+    for name, x, shape, dtype in [("obs0", obs0, (n, nobs), "float32"), ("actions", actions, (T, n, nu), "float32")] + \
+                                 [(name, given[name], (T,) + step, dtype) for name, step, dtype in _tape_table(n, nobs)]:
+        if x is not None:
+            _check_device_buffer(who, name, x, shape, dtype)
     if terminal is not None and not terminal_enabled:
         raise ValueError("rollout_policy: a terminal tape needs terminal observations enabled (enable_terminal_obs)")
     spl = T if steps_per_launch is None else int(steps_per_launch)
     if spl < 1:
         raise ValueError("rollout_policy: steps_per_launch must be >= 1, not %d" % spl)
     return T, spl
-
-
-def _check_device_buffer(who, name, x, shape, dtype):
-    """``x``: a raw device pointer (int), taken as given, or a described object (torch tensor): ``shape``, ``dtype``, contiguous, on the device."""
-    if not hasattr(x, "data_ptr"):
-        if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
-            raise ValueError("%s: %s must be a device tensor (data_ptr()) or a raw device pointer (int), not %s" % (who, name, type(x).__name__))
-        return
-    if tuple(x.shape) != tuple(shape):
-        raise ValueError("%s: %s must be %s, not %s" % (who, name, list(shape), list(x.shape)))
-    if dtype not in str(x.dtype):
-        raise ValueError("%s: %s must be %s, not %s" % (who, name, dtype, x.dtype))
-    if not x.is_contiguous():
-        raise ValueError("%s: %s must be contiguous" % (who, name))
-    if hasattr(x, "is_cuda") and not x.is_cuda:
-        raise ValueError("%s: %s must live on the device" % (who, name))
 
 
 def check_obs_norm_args(nobs, mean, inv_std, clip):
@@ -398,9 +360,7 @@ def check_obs_norm_args(nobs, mean, inv_std, clip):
     who = "set_policy_obs_norm"
     if (mean is None) != (inv_std is None):
         raise ValueError("%s: mean and inv_std go together (both None: off)" % who)
-    if isinstance(clip, bool) or not isinstance(clip, (int, float, np.integer, np.floating)):
-        raise ValueError("%s: clip must be a number, not %s" % (who, type(clip).__name__))
-    clip = float(clip)
+    clip = _number(who, "clip", clip)
     if not np.isfinite(clip) or clip < 0:
         raise ValueError("%s: clip must be finite and >= 0 (0: no clamp), not %r" % (who, clip))
     if mean is not None:
@@ -418,8 +378,10 @@ def check_gae_args(n, reward, done, value, last_value, term_value=None, gamma=0.
     for name, x in (("reward", reward), ("done", done), ("value", value), ("last_value", last_value)):
         if x is None:
             raise ValueError("%s: %s is None" % (who, name))
+    tapes = (("reward", reward, "float32"), ("done", done, "uint8"), ("value", value, "float32"), ("term_value", term_value, "float32"),
+             ("adv", adv, "float32"), ("ret", ret, "float32"))
     T = None if n_steps is None else int(n_steps)
-    for name, x in (("reward", reward), ("done", done), ("value", value), ("term_value", term_value), ("adv", adv), ("ret", ret)):
+    for name, x, _ in tapes:
         if x is not None and hasattr(x, "data_ptr") and len(x.shape) == 2:
             if T is None:
                 T = int(x.shape[0])
@@ -429,20 +391,19 @@ def check_gae_args(n, reward, done, value, last_value, term_value=None, gamma=0.
         raise ValueError("%s: raw pointers need n_steps" % who)
     if T < 1:
         raise ValueError("%s: T must be >= 1, not %d" % (who, T))
-    for name, x, dtype in (("reward", reward, "float32"), ("done", done, "uint8"), ("value", value, "float32"),
-                           ("term_value", term_value, "float32"), ("adv", adv, "float32"), ("ret", ret, "float32")):
+    for name, x, dtype in tapes:
         if x is not None:
             _check_device_buffer(who, name, x, (T, n), dtype)
     _check_device_buffer(who, "last_value", last_value, (n,), "float32")
     out = []
     for name, g in (("gamma", gamma), ("lam", lam)):
-        if isinstance(g, bool) or not isinstance(g, (int, float, np.integer, np.floating)):
-            raise ValueError("%s: %s must be a number, not %s" % (who, name, type(g).__name__))
-        g = float(g)
+        g = _number(who, name, g)
         if not (0.0 <= g <= 1.0):
             raise ValueError("%s: %s must be in [0, 1], not %r" % (who, name, g))
         out.append(g)
     return T, out[0], out[1]
+
+
 
 
 class ObsNorm:
@@ -487,7 +448,16 @@ class ObsNorm:
         return y.clamp(-self.clip, self.clip) if self.clip > 0 else y
 
 
-SNAPSHOT_BLOB_HEADER = 64         # bytes in front of the payload of lm_snapshot_export (include/locohip.h)
+def check_terminal_obs_args(n, nobs, out):
+    """The argument check of :meth:`HipBatch.enable_terminal_obs`, without a device: ``out`` None (the batch's own buffer), a described
+    object (torch tensor), which is checked — float32 [n, nobs], contiguous, on the device — or anything else, which ``int()`` makes the
+    raw device pointer. Raises ValueError."""
+    if hasattr(out, "data_ptr"):
+        _check_device_buffer("terminal observations", "the buffer", out, (n, nobs), "float32",
+                             say={"shape": "%(who)s: %(name)s must be %(shape)s, not %(got_tuple)s"})
+
+
+SNAPSHOT_BLOB_HEADER = 64        # bytes in front of the payload of lm_snapshot_export (include/locohip.h)
 
 
 def check_restore_args(n, src=None, mask=None, snapshot=None, batch=None):
@@ -510,15 +480,9 @@ def check_restore_args(n, src=None, mask=None, snapshot=None, batch=None):
         return "all", None
     name, x = ("src", src) if src is not None else ("mask", mask)
     if hasattr(x, "data_ptr"):
-        if tuple(x.shape) != (n,):
-            raise ValueError("restore: %s must be [%d], not %s" % (name, n, list(x.shape)))
-        want = "int32" if src is not None else "bool"
-        if want not in str(x.dtype):
-            raise ValueError("restore: a %s tensor must be %s, not %s" % (name, want, x.dtype))
-        if not x.is_contiguous():
-            raise ValueError("restore: %s must be contiguous" % name)
-        if hasattr(x, "is_cuda") and not x.is_cuda:
-            raise ValueError("restore: a %s tensor must live on the device (host values: a numpy array or a list)" % name)
+        _check_device_buffer("restore", name, x, (n,), "int32" if src is not None else "bool",
+                             say={"dtype": "%(who)s: a %(name)s tensor must be %(dtype)s, not %(got)s",
+                                  "device": "%(who)s: a %(name)s tensor must live on the device (host values: a numpy array or a list)"})
         return ("device" if src is not None else "device_mask"), x
     if isinstance(x, (str, bytes)) or np.ndim(x) == 0:
         raise ValueError("restore: %s must be a sequence of %d entries, not %s" % (name, n, type(x).__name__))
@@ -555,7 +519,7 @@ class HipModel:
             raise BackendError("no HIP device visible: the batched simulator needs an MI355X (no CPU fallback)")
         cm = np.ascontiguousarray(chain_model, dtype=np.float64)
         h = C.c_void_p()
-        _check(lib.lm_model_create(cm.ctypes.data_as(_D), len(cm), device, C.byref(h)))
+        _check(lib.lm_model_create(_ptr(cm, _D), len(cm), device, C.byref(h)))
         self._h = h
         self._lib = lib                      # kept on the object: module globals are gone when __del__ runs at interpreter exit
         d = Dims()
@@ -666,18 +630,18 @@ class HipBatch:
     def replay_marks(self, reset=False):
         """Per environment: did the replay kernel run one of its control steps since the marks were last cleared?"""
         out = np.empty(self.n, dtype=np.uint8)
-        _check(self._lib.lm_get_replay_marks(self._h, out.ctypes.data_as(_U8), int(bool(reset))))
+        _check(self._lib.lm_get_replay_marks(self._h, _ptr(out, _U8), int(bool(reset))))
         return out != 0
 
     def set_state(self, qpos, qvel, mask=None):
         q, v = _f32(qpos, (self.n, self.nq)), _f32(qvel, (self.n, self.nv))
         keep, mp = _mask(mask, self.n)
-        _check(self._lib.lm_set_state(self._h, _fp(q), _fp(v), mp))
+        _check(self._lib.lm_set_state(self._h, _ptr(q), _ptr(v), mp))
 
     def get_state(self):
         q = np.empty((self.n, self.nq), dtype=np.float32)
         v = np.empty((self.n, self.nv), dtype=np.float32)
-        _check(self._lib.lm_get_state(self._h, _fp(q), _fp(v)))
+        _check(self._lib.lm_get_state(self._h, _ptr(q), _ptr(v)))
         return q, v
 
     def step_device(self, action=None, obs=None, reward=None, done=None, stream=None, sync=True):
@@ -696,11 +660,11 @@ class HipBatch:
         """Per-environment joint parameters [n, nv] (domain randomisation); None leaves a parameter as it is."""
         arrs = [None if x is None else _f32(x, (self.n, self.nv)) for x in (damping, stiffness, frictionloss)]
         keep, mp = _mask(mask, self.n)
-        _check(self._lib.lm_set_dof_params(self._h, *[None if x is None else _fp(x) for x in arrs], mp))
+        _check(self._lib.lm_set_dof_params(self._h, *[None if x is None else _ptr(x) for x in arrs], mp))
 
     def get_dof_params(self):
         out = [np.empty((self.n, self.nv), dtype=np.float32) for _ in range(3)]
-        _check(self._lib.lm_get_dof_params(self._h, *[_fp(x) for x in out]))
+        _check(self._lib.lm_get_dof_params(self._h, *[_ptr(x) for x in out]))
         return dict(damping=out[0], stiffness=out[1], frictionloss=out[2])
 
     def set_dof_randomization(self, spec):
@@ -709,7 +673,7 @@ class HipBatch:
             _check(self._lib.lm_set_dof_randomization(self._h, None))
             return
         s = _f32(spec, (3, self.nv, 3))
-        _check(self._lib.lm_set_dof_randomization(self._h, _fp(s)))
+        _check(self._lib.lm_set_dof_randomization(self._h, _ptr(s)))
 
     def set_model_variants(self, tables):
         """``tables``: list of (record, geom table, geom-pair table) from ``lowering.variant_tables`` — the pool of randomised
@@ -723,7 +687,7 @@ class HipBatch:
         gt = np.ascontiguousarray(np.stack([t[1] for t in tables]), dtype=np.float32)
         npair = len(tables[0][2])
         gpt = np.ascontiguousarray(np.stack([t[2] for t in tables]), dtype=np.float32) if npair else None
-        _check(self._lib.lm_set_model_variants(self._h, _fp(rec), _fp(gt), _fp(gpt) if gpt is not None else None, npair, len(tables)))
+        _check(self._lib.lm_set_model_variants(self._h, _ptr(rec), _ptr(gt), _ptr(gpt) if gpt is not None else None, npair, len(tables)))
         self.n_variants = len(tables)
         self._compiler_on = False
 
@@ -752,8 +716,8 @@ class HipBatch:
         rec, gt = _f32(nominal_tables[0], (len(nominal_tables[0]),)), _f32(nominal_tables[1], (len(nominal_tables[1]),))
         npair = len(nominal_tables[2])
         gpt = _f32(nominal_tables[2], (npair,)) if npair else None
-        _check(self._lib.lm_set_model_compiler(self._h, ib.ctypes.data_as(C.POINTER(C.c_int32)), len(ib), db.ctypes.data_as(C.POINTER(C.c_double)),
-                                               len(db), _fp(rec), _fp(gt), _fp(gpt) if gpt is not None else None, npair, int(seed) & (2 ** 64 - 1)))
+        _check(self._lib.lm_set_model_compiler(self._h, _ptr(ib, _I32), len(ib), _ptr(db, _D),
+                                               len(db), _ptr(rec), _ptr(gt), _ptr(gpt) if gpt is not None else None, npair, int(seed) & (2 ** 64 - 1)))
         self.n_variants = self.n
         self._compiler_on = True
         self.n_model_draws = int(ib[4])
@@ -768,20 +732,20 @@ class HipBatch:
         """(draws [n, n_draw] float64 of every environment's CURRENT model, models each environment has had [n])."""
         d = np.empty((self.n, self.n_model_draws), dtype=np.float64)
         g = np.empty(self.n, dtype=np.uint32)
-        _check(self._lib.lm_get_model_draws(self._h, d.ctypes.data_as(C.POINTER(C.c_double)), g.ctypes.data_as(C.POINTER(C.c_uint32))))
+        _check(self._lib.lm_get_model_draws(self._h, _ptr(d, _D), _ptr(g, C.POINTER(C.c_uint32))))
         return d, g
 
     def get_model_tables(self, env, sizes=None):
         """(record, geom table, geom-pair table) environment ``env`` runs on."""
         nr, ng, npair = sizes if sizes is not None else self._table_sizes
         rec, gt, gpt = np.empty(nr, dtype=np.float32), np.empty(ng, dtype=np.float32), np.empty(npair, dtype=np.float32)
-        _check(self._lib.lm_get_model_tables(self._h, int(env), _fp(rec), _fp(gt), _fp(gpt) if npair else None))
+        _check(self._lib.lm_get_model_tables(self._h, int(env), _ptr(rec), _ptr(gt), _ptr(gpt) if npair else None))
         return rec, gt, gpt
 
     def set_variant_index(self, index, mask=None):
         idx = np.ascontiguousarray(np.broadcast_to(np.asarray(index, dtype=np.int32), (self.n,)))
         keep, mp = _mask(mask, self.n)
-        _check(self._lib.lm_set_variant_index(self._h, idx.ctypes.data_as(C.POINTER(C.c_int32)), mp))
+        _check(self._lib.lm_set_variant_index(self._h, _ptr(idx, _I32), mp))
 
     def set_variant_rows(self, rows_per_variant):
         """The reset table is n_variants blocks of ``rows_per_variant`` rows: a device-side restart from row i puts the environment
@@ -790,18 +754,18 @@ class HipBatch:
 
     def get_variant_index(self):
         idx = np.zeros(self.n, dtype=np.int32)
-        _check(self._lib.lm_get_variant_index(self._h, idx.ctypes.data_as(C.POINTER(C.c_int32))))
+        _check(self._lib.lm_get_variant_index(self._h, _ptr(idx, _I32)))
         return idx
 
     def set_activation(self, act, mask=None):
         """Muscle activations [n, na] (set_state zeroes them like mj_resetData; this is for checkpoints and tests)."""
         a = _f32(act, (self.n, self.na))
         keep, mp = _mask(mask, self.n)
-        _check(self._lib.lm_set_activation(self._h, _fp(a), mp))
+        _check(self._lib.lm_set_activation(self._h, _ptr(a), mp))
 
     def get_activation(self):
         a = np.empty((self.n, self.na), dtype=np.float32)
-        _check(self._lib.lm_get_activation(self._h, _fp(a)))
+        _check(self._lib.lm_get_activation(self._h, _ptr(a)))
         return a
 
     def set_goal(self, goal, mask=None):
@@ -809,14 +773,14 @@ class HipBatch:
             return
         g = _f32(goal, (self.n, self.ngoal))
         keep, mp = _mask(mask, self.n)
-        _check(self._lib.lm_set_goal(self._h, _fp(g), mp))
+        _check(self._lib.lm_set_goal(self._h, _ptr(g), mp))
 
     def step(self, action):
         a = _f32(action, (self.n, self.nu))
         obs = np.empty((self.n, self.nobs), dtype=np.float32)
         rew = np.empty(self.n, dtype=np.float32)
         done = np.empty(self.n, dtype=np.uint8)
-        _check(self._lib.lm_step(self._h, _fp(a), _fp(obs), _fp(rew), done.ctypes.data_as(_U8)))
+        _check(self._lib.lm_step(self._h, _ptr(a), _ptr(obs), _ptr(rew), _ptr(done, _U8)))
         # done byte: bit 0 = absorbing state, bit 1 = the device ended the episode in this step (restarted it from the
         # reset table, or the horizon was reached)
         self.last_restarted = (done & 2) != 0
@@ -828,7 +792,7 @@ class HipBatch:
             _check(self._lib.lm_batch_set_active(self._h, None, 0))
             return
         ids = np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
-        _check(self._lib.lm_batch_set_active(self._h, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids)))
+        _check(self._lib.lm_batch_set_active(self._h, _ptr(ids, _I32), len(ids)))
 
     PINNED_SLOTS = 4
 
@@ -838,12 +802,12 @@ class HipBatch:
             _check(self._lib.lm_set_obs_order(self._h, None, 0))
         else:
             p = np.ascontiguousarray(perm, dtype=np.int32)
-            _check(self._lib.lm_set_obs_order(self._h, p.ctypes.data_as(C.POINTER(C.c_int32)), len(p)))
+            _check(self._lib.lm_set_obs_order(self._h, _ptr(p, _I32), len(p)))
 
     def _pinned_views(self):
         views = []
         for slot in range(self.PINNED_SLOTS):
-            o, r, d = C.POINTER(C.c_double)(), C.POINTER(C.c_double)(), _U8()
+            o, r, d = _D(), _D(), _U8()
             _check(self._lib.lm_pinned_slot(self._h, slot, C.byref(o), C.byref(r), C.byref(d)))
             arrs = []
             for ptr, ct, dt, shape in ((o, C.c_double, np.float64, (self.n, self.nobs)), (r, C.c_double, np.float64, (self.n,)), (d, C.c_uint8, np.uint8, (self.n,))):
@@ -863,7 +827,7 @@ class HipBatch:
             self._pinned = self._pinned_views()
             self._slot = -1
         self._slot = (self._slot + 1) % self.PINNED_SLOTS
-        _check(self._lib.lm_step_pinned(self._h, action64.ctypes.data_as(C.POINTER(C.c_double)), self._slot))
+        _check(self._lib.lm_step_pinned(self._h, _ptr(action64, _D), self._slot))
         obs, rew, done = self._pinned[self._slot]
         self.last_restarted = (done & 2) != 0
         if self._term_on:
@@ -877,21 +841,8 @@ class HipBatch:
         observation of the state it reached — not the restarted episode's first — into row e of a float32 buffer [n, nobs].
         ``out`` None: a zero-filled buffer owned by the batch, read with :meth:`terminal_obs`; otherwise a device pointer (int) or a
         torch tensor [n, nobs], float32, contiguous, which the batch keeps alive until :meth:`disable_terminal_obs` / :meth:`close`."""
-        ptr = None
-        if out is not None:
-            if hasattr(out, "data_ptr"):
-                if tuple(out.shape) != (self.n, self.nobs):
-                    raise ValueError("terminal observations: the buffer must be [%d, %d], not %s" % (self.n, self.nobs, tuple(out.shape)))
-                if "float32" not in str(out.dtype):
-                    raise ValueError("terminal observations: the buffer must be float32, not %s" % (out.dtype,))
-                if not out.is_contiguous():
-                    raise ValueError("terminal observations: the buffer must be contiguous")
-                if hasattr(out, "is_cuda") and not out.is_cuda:
-                    raise ValueError("terminal observations: the buffer must live on the device")
-                ptr = C.c_void_p(int(out.data_ptr()))
-            else:
-                ptr = C.c_void_p(int(out))
-        _check(self._lib.lm_set_terminal_obs(self._h, 1, ptr))
+        check_terminal_obs_args(self.n, self.nobs, out)
+        _check(self._lib.lm_set_terminal_obs(self._h, 1, _dev_ptr(out)))
         self._term_out = out
         self._term_on = True
 
@@ -903,13 +854,13 @@ class HipBatch:
     def terminal_obs(self):
         """The terminal-observation buffer as a host float32 array [n, nobs] (the kernel's column order), after the last step."""
         out = np.empty((self.n, self.nobs), dtype=np.float32)
-        _check(self._lib.lm_get_terminal_obs(self._h, _fp(out)))
+        _check(self._lib.lm_get_terminal_obs(self._h, _ptr(out)))
         return out
 
     def _pinned_term_views(self):
         views = []
         for slot in range(self.PINNED_SLOTS):
-            t = C.POINTER(C.c_double)()
+            t = _D()
             _check(self._lib.lm_pinned_terminal_obs(self._h, slot, C.byref(t)))
             buf = (C.c_double * (self.n * self.nobs)).from_address(C.addressof(t.contents))
             buf._owner = self
@@ -919,7 +870,7 @@ class HipBatch:
     def set_reset_table(self, rows, seed=0, global_env_offset=0):
         r = _f32(rows)
         assert r.ndim == 2 and r.shape[1] == self.nq + self.nv + self.ngoal
-        _check(self._lib.lm_set_reset_table(self._h, _fp(r), r.shape[0], int(seed), int(global_env_offset)))
+        _check(self._lib.lm_set_reset_table(self._h, _ptr(r), r.shape[0], int(seed), int(global_env_offset)))
 
     def set_auto_reset(self, enabled, horizon=0):
         _check(self._lib.lm_set_auto_reset(self._h, int(bool(enabled)), int(horizon)))
@@ -1077,10 +1028,10 @@ class HipBatch:
         it = np.zeros(self.n, np.int32)
         out = ForwardOut()
         for k, arr in res.items():
-            setattr(out, k, _fp(arr))
-        out.ncon = ncon.ctypes.data_as(C.POINTER(C.c_int))
-        out.solver_iter = it.ctypes.data_as(C.POINTER(C.c_int))
-        _check(self._lib.lm_forward_debug(self._h, _fp(a), C.byref(out)))
+            setattr(out, k, _ptr(arr))
+        out.ncon = _ptr(ncon, C.POINTER(C.c_int))
+        out.solver_iter = _ptr(it, C.POINTER(C.c_int))
+        _check(self._lib.lm_forward_debug(self._h, _ptr(a), C.byref(out)))
         res["ncon"], res["solver_iter"] = ncon, it
         return res
 
@@ -1093,7 +1044,7 @@ class HipBatch:
         """Validity flags of the last control step per environment (``lm_get_flags``): 1 dropped contact, 2 self pair without a
         collider in reach, 4 collider-less geom at the floor."""
         out = np.empty(self.n, dtype=np.uint8)
-        _check(self._lib.lm_get_flags(self._h, out.ctypes.data_as(_U8)))
+        _check(self._lib.lm_get_flags(self._h, _ptr(out, _U8)))
         return out
 
     def sync(self):

@@ -889,6 +889,18 @@ struct StreamScope {
   }
   ~StreamScope() { (void)leave(); }
 };
+// `queue(stream)` inside a scope: enter, queue, leave, and wait for the stream if asked. The per-thread HIP error state is shared with
+// whoever else uses HIP in this process: what they left behind is dropped, so that the check after `queue` reports OUR launches
+extern "C++" template <class Queue> static int on_stream(lm_batch* b, void* stream, int sync, Queue queue) {
+  StreamScope scope(b, stream);
+  if (scope.enter()) return 1;
+  (void)hipGetLastError();
+  if (queue(scope.used)) return 1;
+  HIPCHK(hipGetLastError());
+  if (scope.leave()) return 1;
+  if (sync) HIPCHK(hipStreamSynchronize(scope.used));
+  return 0;
+}
 
 // Where the control steps of one call take their actions and leave their results: the first step's pointer and the stride from one
 // control step to the next, in elements (0: every step at the same rows). `action_mode` is the kernels' (0: `action`, 1: zero, 2:
@@ -904,6 +916,15 @@ struct StepIO {
 // the batch's own rows, overwritten by every control step: what lm_step* and the policy-free rollouts write
 static StepIO own_rows(lm_batch* b, int action_mode, const float* action) {
   return {action_mode, b->seed, action, 0, b->obs, 0, b->reward, 0, b->done, 0, nullptr, 0};
+}
+// the tapes of lm_rollout_tape / lm_rollout_policy, one row set per control step. A tape that is not given: the batch's own rows as in
+// lm_step_device, stride 0 — every control step overwrites them
+static void record_on_tapes(StepIO* io, const lm_batch* b, float* d_obs, float* d_reward, uint8_t* d_done, float* d_term) {
+  const long long N = b->N, nobs = b->m->T.nobs;
+  if (d_obs) { io->obs = d_obs; io->obs_stride = N * nobs; }
+  if (d_reward) { io->reward = d_reward; io->reward_stride = N; }
+  if (d_done) { io->done = d_done; io->done_stride = N; }
+  if (d_term) { io->term = d_term; io->term_stride = N * nobs; }
 }
 
 // THE launch path of lm_step*, lm_rollout_fused and lm_rollout_tape: queues `n_steps` control steps on `stream`, `steps_per_launch` of
@@ -970,6 +991,19 @@ static int drain_stats(lm_batch* b) {
     b->acc.unhandled_geoms += x.unhandled; b->acc.linesearch_evals += x.ls_evals; b->acc.linesearch_capped += x.ls_capped; b->acc.steps_with_8plus_iters += x.it_ge8;
     b->acc.self_proximity += x.selfprox; b->acc.self_contacts += x.selfcon; b->acc.replayed_env_steps += x.replayed; b->acc.own_manifold_contacts += x.natown;
   }
+  return 0;
+}
+
+// the end of a rollout behind queue_steps(..., timed = true): wait for the span (`wait` false: the call returns with the steps queued),
+// add its time to the batch's and, with `drain`, the device's counters; `stats`: the totals, with this span's time
+static int finish_rollout(lm_batch* b, bool wait, bool drain, lm_stats* stats) {
+  if (!wait) return 0;
+  HIPCHK(hipEventSynchronize(b->ev1));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, b->ev0, b->ev1));
+  b->acc.kernel_ms += ms;
+  if (drain && drain_stats(b)) return 1;
+  if (stats) { *stats = b->acc; stats->kernel_ms = ms; }
   return 0;
 }
 
@@ -1168,10 +1202,7 @@ int lm_step_device(lm_batch* b, const float* d_action, float* d_obs, float* d_re
   if (d_obs) io.obs = d_obs;
   if (d_reward) io.reward = d_reward;
   if (d_done) io.done = d_done;
-  StreamScope scope(b, stream);
-  if (scope.enter() || queue_steps(b, scope.used, io, 1, 1, false) || scope.leave()) return 1;
-  if (sync) HIPCHK(hipStreamSynchronize(scope.used));
-  return 0;
+  return on_stream(b, stream, sync, [&](hipStream_t s) { return queue_steps(b, s, io, 1, 1, false); });
 }
 
 int lm_set_reset_table(lm_batch* b, const float* rows, int n_rows, uint64_t seed, int64_t global_env_offset) {
@@ -1199,13 +1230,7 @@ int lm_rollout_fused(lm_batch* b, int n_steps, int steps_per_launch, int action_
   StepIO io = own_rows(b, action_mode == 0 ? 1 : 2, nullptr);   // kernel: 1 = zero action, 2 = random
   io.seed = b->seed ^ (seed * 0x9E3779B97F4A7C15ull);
   if (queue_steps(b, b->stream, io, n_steps, steps_per_launch, true)) return 1;
-  HIPCHK(hipEventSynchronize(b->ev1));
-  float ms = 0;
-  HIPCHK(hipEventElapsedTime(&ms, b->ev0, b->ev1));
-  if (drain_stats(b)) return 1;
-  b->acc.kernel_ms += ms;
-  if (stats) { *stats = b->acc; stats->kernel_ms = ms; }
-  return 0;
+  return finish_rollout(b, true, true, stats);
 }
 
 int lm_rollout_tape(lm_batch* b, int n_steps, int steps_per_launch, const float* d_actions, long long action_step_stride,
@@ -1219,26 +1244,12 @@ int lm_rollout_tape(lm_batch* b, int n_steps, int steps_per_launch, const float*
   if (!d_actions) return fail("lm_rollout_tape: d_actions is null (policy-free rollouts: lm_rollout_fused)");
   if (action_step_stride != 0 && action_step_stride != N * T.nu) return fail("lm_rollout_tape: action_step_stride must be n_envs * nu (a tape) or 0 (action repeat)");
   if (d_term && !b->term_obs) return fail("lm_rollout_tape: d_term needs terminal observations enabled (lm_set_terminal_obs)");
-  // the batch's own seed: a tape launch restarts episodes exactly like lm_step*. A tape that is not given: the batch's own rows as in
-  // lm_step_device, stride 0 — every control step overwrites them
+  // the batch's own seed: a tape launch restarts episodes exactly like lm_step*
   StepIO io = own_rows(b, 0, d_actions);
   io.action_stride = action_step_stride;
-  if (d_obs) { io.obs = d_obs; io.obs_stride = N * T.nobs; }
-  if (d_reward) { io.reward = d_reward; io.reward_stride = N; }
-  if (d_done) { io.done = d_done; io.done_stride = N; }
-  if (d_term) { io.term = d_term; io.term_stride = N * T.nobs; }
-  StreamScope scope(b, stream);
-  if (scope.enter() || queue_steps(b, scope.used, io, n_steps, steps_per_launch, true) || scope.leave()) return 1;
-  if (!sync) return 0;
-  HIPCHK(hipEventSynchronize(b->ev1));
-  float ms = 0;
-  HIPCHK(hipEventElapsedTime(&ms, b->ev0, b->ev1));
-  b->acc.kernel_ms += ms;
-  if (stats) {
-    if (drain_stats(b)) return 1;
-    *stats = b->acc; stats->kernel_ms = ms;
-  }
-  return 0;
+  record_on_tapes(&io, b, d_obs, d_reward, d_done, d_term);
+  if (on_stream(b, stream, 0, [&](hipStream_t s) { return queue_steps(b, s, io, n_steps, steps_per_launch, true); })) return 1;
+  return finish_rollout(b, sync, stats != nullptr, stats);
 }
 
 int lm_rollout_policy(lm_batch* b, const lm_mlp_policy* p, int n_steps, int steps_per_launch, uint64_t noise_seed,
@@ -1269,23 +1280,10 @@ int lm_rollout_policy(lm_batch* b, const lm_mlp_policy* p, int n_steps, int step
   if (!b->pol_sink && batch_array(b, &b->pol_sink, (size_t)N * T.nobs)) return 1;
   StepIO io = own_rows(b, 0, d_actions);
   io.action_stride = N * T.nu;
-  if (d_obs) { io.obs = d_obs; io.obs_stride = N * T.nobs; }
-  if (d_reward) { io.reward = d_reward; io.reward_stride = N; }
-  if (d_done) { io.done = d_done; io.done_stride = N; }
-  if (d_term) { io.term = d_term; io.term_stride = N * T.nobs; }
+  record_on_tapes(&io, b, d_obs, d_reward, d_done, d_term);
   const PolicyCall pol = {*p, d_obs0 ? d_obs0 : b->obs, noise_seed};
-  StreamScope scope(b, stream);
-  if (scope.enter() || queue_steps(b, scope.used, io, n_steps, steps_per_launch, true, &pol) || scope.leave()) return 1;
-  if (!sync) return 0;
-  HIPCHK(hipEventSynchronize(b->ev1));
-  float ms = 0;
-  HIPCHK(hipEventElapsedTime(&ms, b->ev0, b->ev1));
-  b->acc.kernel_ms += ms;
-  if (stats) {
-    if (drain_stats(b)) return 1;
-    *stats = b->acc; stats->kernel_ms = ms;
-  }
-  return 0;
+  if (on_stream(b, stream, 0, [&](hipStream_t s) { return queue_steps(b, s, io, n_steps, steps_per_launch, true, &pol); })) return 1;
+  return finish_rollout(b, sync, stats != nullptr, stats);
 }
 
 // Generalised advantage estimation over the tapes (locohip.h lm_tape_gae): one environment per lane, so that every row [t][.] of a tape
@@ -1337,14 +1335,10 @@ int lm_tape_gae(lm_batch* b, int n_steps, const float* d_reward, const uint8_t* 
   HIPCHK(hipSetDevice(b->m->device));
   const lmg::GaeArgs a = {d_reward, d_value, d_last_value, d_term_value, d_done, gamma, lam, d_adv, d_ret, n_steps, (long long)b->N};
   // on the given stream behind everything the batch has in flight (the rollout that fills the tapes), as the snapshot copy is
-  StreamScope scope(b, stream);
-  if (scope.enter()) return 1;
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(lmg::gae_kernel, dim3((unsigned)((a.N + lmg::kGaeBlock - 1) / lmg::kGaeBlock)), dim3(lmg::kGaeBlock), 0, scope.used, a);
-  HIPCHK(hipGetLastError());
-  if (scope.leave()) return 1;
-  if (sync) HIPCHK(hipStreamSynchronize(scope.used));
-  return 0;
+  return on_stream(b, stream, sync, [&](hipStream_t s) {
+    hipLaunchKernelGGL(lmg::gae_kernel, dim3((unsigned)((a.N + lmg::kGaeBlock - 1) / lmg::kGaeBlock)), dim3(lmg::kGaeBlock), 0, s, a);
+    return 0;
+  });
 }
 
 int lm_rollout(lm_batch* b, int n_steps, int action_mode, uint64_t seed, lm_stats* stats) {
@@ -1549,15 +1543,11 @@ int lm_snapshot_save(lm_batch* b, lm_snapshot* s, void* stream, int sync) {
   HIPCHK(hipSetDevice(b->m->device));
   lms::Table t;
   if (!snap_table(b, s->flags, &t) || t.bytes != s->bytes) return fail("lm_snapshot_save: the snapshot's layout does not match the batch");
-  StreamScope scope(b, stream);
-  if (scope.enter()) return 1;
-  (void)hipGetLastError();
-  lms::launch_copy(t, s->data, nullptr, 0, scope.used);
-  s->step_index = b->step_index; s->saved = true;
-  HIPCHK(hipGetLastError());
-  if (scope.leave()) return 1;
-  if (sync) HIPCHK(hipStreamSynchronize(scope.used));
-  return 0;
+  return on_stream(b, stream, sync, [&](hipStream_t on) {
+    lms::launch_copy(t, s->data, nullptr, 0, on);
+    s->step_index = b->step_index; s->saved = true;
+    return 0;
+  });
 }
 
 int lm_snapshot_restore(lm_batch* b, const lm_snapshot* s, const int32_t* d_src, void* stream, int sync) {
@@ -1567,15 +1557,11 @@ int lm_snapshot_restore(lm_batch* b, const lm_snapshot* s, const int32_t* d_src,
   HIPCHK(hipSetDevice(b->m->device));
   lms::Table t;
   if (!snap_table(b, s->flags, &t) || t.bytes != s->bytes) return fail("lm_snapshot_restore: the snapshot's layout does not match the batch");
-  StreamScope scope(b, stream);
-  if (scope.enter()) return 1;
-  (void)hipGetLastError();
-  lms::launch_copy(t, s->data, d_src, 1, scope.used);
-  if (!d_src) b->step_index = s->step_index;      // every environment is back at the save: so is the count that keys the random actions
-  HIPCHK(hipGetLastError());
-  if (scope.leave()) return 1;
-  if (sync) HIPCHK(hipStreamSynchronize(scope.used));
-  return 0;
+  return on_stream(b, stream, sync, [&](hipStream_t on) {
+    lms::launch_copy(t, s->data, d_src, 1, on);
+    if (!d_src) b->step_index = s->step_index;      // every environment is back at the save: so is the count that keys the random actions
+    return 0;
+  });
 }
 
 int lm_snapshot_export(lm_batch* b, const lm_snapshot* s, void* host, long long n) {
