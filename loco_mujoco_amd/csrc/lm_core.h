@@ -28,6 +28,7 @@
 #include <math.h>
 #include <type_traits>
 #include "../../include/lm_layout.h"
+#include "lm_families.h"      // (the A/B switch LM_HESS_ENV_VOTE)
 
 #define LM_PAIR_PAD 0.03f     // metres added to the reach of the link-pair list (lowering.PAIR_PAD)
 #ifndef LM_DEV_COLD
@@ -3373,6 +3374,11 @@ LM_DEV void forward(const float* cm, int c, const Params& P, float* qr, float* v
 #else
   constexpr bool kJarIncr = true, kMaIncr = MC < 6;
 #endif
+  // The Hessian pass of kernels with elliptic contacts (lm_families.h LM_HESS_ENV_VOTE): an environment one of whose floor contacts with a
+  // Hessian block has condim > 3 runs ALL its floor blocks through the 6-wide instantiation of `accumulate` (below), so that the lanes of a
+  // collapsed quadruped — condim-6 feet and condim-3 shins in every pass — no longer execute the 6-wide and the 3-wide code one after
+  // the other.
+  constexpr bool kHessEnvVote = LM_HESS_ENV_VOTE != 0 && CONE != 0;
   float qf_r[6], qf_c[MC];      // constraint forces in joint space
 #pragma unroll
   for (int i = 0; i < 6; i++) qf_r[i] = 0;
@@ -3452,6 +3458,7 @@ LM_DEV void forward(const float* cm, int c, const Params& P, float* qr, float* v
       // (Jaref += alpha Jv). LM_JAR_RECOMPUTE: rounds 1-4 (rebuilt in every iteration), for A/B builds.
 
       const bool fresh_rows = !kJarIncr;          // (the first iteration starts from the residuals the warm start left: cost_at)
+      bool wide_slot = false;                     // one of MY floor slots is a condim > 3 contact with a Hessian block (the vote in front of hess_slot)
       if ((nslot > 0 || any_pair) && !(P.ablate & 32)) {
         if (fresh_rows) link_images(ar, ac);
         auto grad_slot = [&](int s, auto is_pair) {
@@ -3493,6 +3500,7 @@ LM_DEV void forward(const float* cm, int c, const Params& P, float* qr, float* v
             for (int j = 0; j < 6; j++) fc[j] = e.f[j];
           }
           SL(s, SL_ZONE) = (float)zone;
+          if (kHessEnvVote && !IP && zone != 0 && dim > 3) wide_slot = true;
           if (zone) {
             if constexpr (IP) {
               V3 n, t1, t2;
@@ -3586,6 +3594,20 @@ LM_DEV void forward(const float* cm, int c, const Params& P, float* qr, float* v
 #pragma unroll
           for (int i = 0; i < 6; i++) if (act_lim_r & (1u << i)) Hrep[tri(i, i)] += lim_D_r[i];
         }
+        // ONE instantiation of `accumulate` per environment. Voted per ENVIRONMENT like `split` (never per wave), at a point all its lanes
+        // reach together. A condim-3 slot on the 6-wide path gives the numbers of the 3-wide one: cone_hessian leaves rows and columns 3-5
+        // of Hc exactly zero (Sc[j] = 0 for j >= dim), so stage 1 adds fma(+-0, x, acc) to an acc that started at +0 — t[0..2] bit for bit
+        // (+0 + +-0 = +0 in round-to-nearest), t[3..5] = +0 — and stage 2 adds fma(+0, x, d) = d. At most the SIGN of an exactly zero d
+        // differs; H += d is then the same value, and nothing downstream of H changes by a rounding. (An environment with non-finite
+        // numbers may carry another NaN: it is reset and counted either way.) So which path a lane takes changes no result — shards,
+        // fused against single-step and replay against regular launches stay bitwise — and a slot with condim > 3 takes the 6-wide path
+        // whatever the vote says.
+        // FLOOR slots only. The self-contact slots (the pair instantiation of hess_slot) keep choosing by their own condim: with them in the
+        // vote the emulator still agreed bit for bit, the device did not (states with self-contacts one ulp off the library before the vote,
+        // tests/test_hessian_paths_gpu.py; floor-contact states equal). Supposed cause: under -ffp-contract=fast the compiler fuses the
+        // shared Hc / row arithmetic of that instantiation differently for the two branches — arithmetic the source states once.
+        bool env_wide = false;
+        if constexpr (kHessEnvVote) env_wide = Q::env_ballot(wide_slot) != 0u;
         auto hess_slot = [&](int s, auto is_pair) {
           constexpr bool IP = decltype(is_pair)::value;
           oz = LM_OPAQUE_ZERO();
@@ -3704,17 +3726,21 @@ LM_DEV void forward(const float* cm, int c, const Params& P, float* qr, float* v
               }
             }
           };
+          const bool wide = CONE != 0 && (dim > 3 || (!IP && env_wide));
+#ifdef LM_HESS_TRACE
+          printf(" hess it %d lane %d rep %d slot %d dim %d zone %d wide %d\n", iters, c, Q::rep(), s, dim, zone, (int)wide);
+#endif
           if constexpr (IP || ROOT_XYZ || MC < 5) {
-            if (CONE != 0 && dim > 3) accumulate(std::integral_constant<int, 6>{}, std::integral_constant<bool, ROOT_XYZ>{});
+            if (wide) accumulate(std::integral_constant<int, 6>{}, std::integral_constant<bool, ROOT_XYZ>{});
             else accumulate(std::integral_constant<int, 3>{}, std::integral_constant<bool, ROOT_XYZ>{});
           } else {
             // the humanoid families serve robots with either kind of root (Atlas, Talos, UnitreeH1 / G1: slides along x, y, z in a root
             // frame that is the world's; the two humanoids: a turned pelvis frame): a uniform branch on the model's flag
             if (P.root_xyz) {
-              if (CONE != 0 && dim > 3) accumulate(std::integral_constant<int, 6>{}, std::true_type{});
+              if (wide) accumulate(std::integral_constant<int, 6>{}, std::true_type{});
               else accumulate(std::integral_constant<int, 3>{}, std::true_type{});
             } else {
-              if (CONE != 0 && dim > 3) accumulate(std::integral_constant<int, 6>{}, std::false_type{});
+              if (wide) accumulate(std::integral_constant<int, 6>{}, std::false_type{});
               else accumulate(std::integral_constant<int, 3>{}, std::false_type{});
             }
           }

@@ -23,6 +23,12 @@
 // their control steps, and 1100 replays per launch at one environment per workgroup cost 129 ms per step (measured, round 4).
 #define LM_SIX_PAIRS 1
 #endif
+#ifndef LM_HESS_ENV_VOTE
+// 1: in the kernels with elliptic contacts (the quadruped's and the generic ones; the pyramidal families compile the 6-wide code out) an
+// environment takes ONE instantiation of the Hessian accumulation per Newton iteration — the 6-wide one as soon as one of its floor
+// contacts with a Hessian block has condim > 3 (lm_core.h kHessEnvVote: same numbers either way). 0: every slot by its own condim, as before.
+#define LM_HESS_ENV_VOTE 1
+#endif
 // One row per family: X(id, MC, NS, RK4, CONE, NM, PM, flags) of struct Family. Ids 1 and 3 (four contact slots per chain) went in round 5.
 // A family listed here and not in FAMILIES of csrc/Makefile, or the reverse, fails when the library is linked: no checker is needed.
 #define LM_GENERIC_FAMILY 6
