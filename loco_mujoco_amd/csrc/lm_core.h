@@ -28,7 +28,7 @@
 #include <math.h>
 #include <type_traits>
 #include "../../include/lm_layout.h"
-#include "lm_families.h"      // (the A/B switch LM_HESS_ENV_VOTE)
+#include "lm_families.h"      // (the A/B switches LM_HESS_ENV_VOTE, LM_DPP_BCAST)
 
 #define LM_PAIR_PAD 0.03f     // metres added to the reach of the link-pair list (lowering.PAIR_PAD)
 #ifndef LM_DEV_COLD
@@ -48,6 +48,11 @@ LM_DEV float lm_u2f(unsigned x) { return __builtin_bit_cast(float, x); }
 #endif
 
 namespace lm {
+
+// A policy MAY also have kDppBcast with rep_bcast_uniform<J>(x), rep_rot<K>(int) and quad_bcast<K>(x) (lm_step.h: the same exchanges as
+// register moves between lanes, four replicas only); one that has not — the emulator's — is asked for rep_bcast / quad_read alone.
+template <class Q, class = void> struct q_dpp_bcast { static constexpr bool value = false; };
+template <class Q> struct q_dpp_bcast<Q, std::void_t<decltype(Q::kDppBcast)>> { static constexpr bool value = Q::kDppBcast; };
 
 struct V3 { float x, y, z; };
 struct alignas(16) F4 { float x, y, z, w; };      // one 128-bit load
@@ -1818,6 +1823,10 @@ LM_DEV void forward(const float* cm, int c, const Params& P, float* qr, float* v
   // through it so that the compiler re-reads them from LDS where they are used instead of hoisting hundreds of
   // loop-invariant constants into registers across the Newton / line-search loops (that is what spilled).
   constexpr bool PAIRS = PM == 1 || PM == 2, NOMPR = PM == 2, DETECT = PM != 0, DETECT_ONLY = PM == 3;
+  // exchanges between replicas and between the lanes of a quad as DPP moves where the policy offers them (lm_families.h LM_DPP_BCAST);
+  // the kernels compiled for the elliptic cone only (the quadruped's): the pyramidal families' code, the generic family's and the
+  // forward-only kernels' (CONE < 0: the cone read at run time) stay what they were
+  constexpr bool kDppBcast = q_dpp_bcast<Q>::value && CONE > 0;
 #ifdef LM_NO_DEFER
   constexpr bool DEFER = false;
 #else
@@ -2153,7 +2162,15 @@ LM_DEV void forward(const float* cm, int c, const Params& P, float* qr, float* v
         }
         // ---- where do my contacts go: after those of the replicas with a smaller geom index in this pass
         int before = 0, total = made;
-        if (Q::kRep > 1) {
+        if constexpr (kDppBcast) {
+          // the other three replicas' counts by row rotation, each with its replica number in the bits above it (made <= 4): sums of
+          // small integers, the same in any order. Source lanes: my chain's lane in the other replicas — they run this trip with me,
+          // the group and geom loop bounds and the group's bounding-sphere test being the same for every replica of a chain.
+          const int mine = made | (Q::rep() << 4);
+          const int o1 = Q::template rep_rot<1>(mine), o2 = Q::template rep_rot<2>(mine), o3 = Q::template rep_rot<3>(mine);
+          before = (((o1 >> 4) < Q::rep()) ? (o1 & 15) : 0) + (((o2 >> 4) < Q::rep()) ? (o2 & 15) : 0) + (((o3 >> 4) < Q::rep()) ? (o3 & 15) : 0);
+          total = made + (o1 & 15) + (o2 & 15) + (o3 & 15);
+        } else if (Q::kRep > 1) {
           total = 0;
 #pragma unroll
           for (int r = 0; r < Q::kRep; r++) { const int n_r = (int)Q::rep_bcast((float)made, r); if (r < Q::rep()) before += n_r; total += n_r; }
@@ -2263,7 +2280,10 @@ LM_DEV void forward(const float* cm, int c, const Params& P, float* qr, float* v
     float gap_min = 3.0e38f;
     if (DETECT) {
       const float s_own = pair_speed;
-      const float s_quad = fmaxf(fmaxf(Q::quad_read(s_own, 0), Q::quad_read(s_own, 1)), fmaxf(Q::quad_read(s_own, 2), Q::quad_read(s_own, 3)));
+      float s_quad;
+      // (DPP: every lane of the quad is here — no branch on lane data encloses this point of the forward pass)
+      if constexpr (kDppBcast) s_quad = fmaxf(fmaxf(Q::template quad_bcast<0>(s_own), Q::template quad_bcast<1>(s_own)), fmaxf(Q::template quad_bcast<2>(s_own), Q::template quad_bcast<3>(s_own)));
+      else s_quad = fmaxf(fmaxf(Q::quad_read(s_own, 0), Q::quad_read(s_own, 1)), fmaxf(Q::quad_read(s_own, 2), Q::quad_read(s_own, 3)));
       first_detect = !pair_slack || *pair_slack == 0.0f;        // nothing known yet (fresh state: the caller starts the slack at 0)
       // Euler: the positions of this pass lie h x (this pass's velocities) from the next pass's. RK4 evaluates its stages at
       // q0 + a h v(previous stage) and ends at q0 + h/6 (v1 + 2 v2 + 2 v3 + v4): two consecutive evaluation points are at most
@@ -2333,9 +2353,17 @@ LM_DEV void forward(const float* cm, int c, const Params& P, float* qr, float* v
         lo = (lo < 0) ? 0 : lo; hi = (hi > kW) ? kW : hi;
         return (hi > lo) ? (mbelow(hi) & ~mbelow(lo)) : (mask_t)0;
       };
+      // (DPP: the pass is entered by whole waves (`detect`), its chunk loop is left on a quad-uniform condition, and the rounds inside it
+      // run to environment-wide bounds — the four lanes of a quad are together wherever they share a number)
       auto share4 = [&](int x, int* out) {
+        if constexpr (kDppBcast) {
+          const float xf = (float)x;
+          out[0] = (int)Q::template quad_bcast<0>(xf); out[1] = (int)Q::template quad_bcast<1>(xf);
+          out[2] = (int)Q::template quad_bcast<2>(xf); out[3] = (int)Q::template quad_bcast<3>(xf);
+        } else {
 #pragma unroll
-        for (int cs = 0; cs < 4; cs++) out[cs] = (int)Q::quad_read((float)x, cs);
+          for (int cs = 0; cs < 4; cs++) out[cs] = (int)Q::quad_read((float)x, cs);
+        }
       };
       int nres_of[4] = {0, 0, 0, 0}, nq_of[4] = {0, 0, 0, 0};
       float gap_of[4] = {3.0e38f, 3.0e38f, 3.0e38f, 3.0e38f};        // smallest clearance seen for a pair of chain cs (this lane's share)
@@ -2841,8 +2869,11 @@ LM_DEV void forward(const float* cm, int c, const Params& P, float* qr, float* v
 #pragma unroll
         for (int cs = 0; cs < 4; cs++) {
           float gq = gap_of[cs];
-          gq = fminf(fminf(Q::quad_read(gq, 0), Q::quad_read(gq, 1)), fminf(Q::quad_read(gq, 2), Q::quad_read(gq, 3)));
-          if (Q::kRep > 1) {
+          if constexpr (kDppBcast) gq = fminf(fminf(Q::template quad_bcast<0>(gq), Q::template quad_bcast<1>(gq)), fminf(Q::template quad_bcast<2>(gq), Q::template quad_bcast<3>(gq)));      // (behind the chunk loop: whole waves)
+          else gq = fminf(fminf(Q::quad_read(gq, 0), Q::quad_read(gq, 1)), fminf(Q::quad_read(gq, 2), Q::quad_read(gq, 3)));
+          if constexpr (kDppBcast) {      // gq is uniform over the quad by now: the replicas' values in the same order
+            gq = fminf(fminf(fminf(fminf(gq, Q::template rep_bcast_uniform<0>(gq)), Q::template rep_bcast_uniform<1>(gq)), Q::template rep_bcast_uniform<2>(gq)), Q::template rep_bcast_uniform<3>(gq));
+          } else if (Q::kRep > 1) {
             float gm_ = gq;
 #pragma unroll
             for (int r = 0; r < Q::kRep; r++) gm_ = fminf(gm_, Q::rep_bcast(gq, r));
@@ -4003,8 +4034,19 @@ LM_DEV void forward(const float* cm, int c, const Params& P, float* qr, float* v
                   const float mine = (r == 0) ? cand[0] : ((r == 1) ? cand[1] : ((r == 2) ? cand[2] : cand[3]));
                   float x1, x2, xm;
                   line(mine, x1, x2, xm);
+                  if constexpr (kDppBcast) {
+                    // x1, x2, xm come out of Q::sum: uniform over the quad, so replica j's value is in any lane of quad j of the row —
+                    // twelve DPP moves, no LDS round trip in the round. Source lanes: `done` and `ls_done` are the same in every lane
+                    // of an environment (they derive from sums over the quad and from the four values all replicas share), so the
+                    // sixteen lanes of the row are here together.
+                    cd1[0] = Q::template rep_bcast_uniform<0>(x1); cd2[0] = Q::template rep_bcast_uniform<0>(x2); cmg[0] = Q::template rep_bcast_uniform<0>(xm);
+                    cd1[1] = Q::template rep_bcast_uniform<1>(x1); cd2[1] = Q::template rep_bcast_uniform<1>(x2); cmg[1] = Q::template rep_bcast_uniform<1>(xm);
+                    cd1[2] = Q::template rep_bcast_uniform<2>(x1); cd2[2] = Q::template rep_bcast_uniform<2>(x2); cmg[2] = Q::template rep_bcast_uniform<2>(xm);
+                    cd1[3] = Q::template rep_bcast_uniform<3>(x1); cd2[3] = Q::template rep_bcast_uniform<3>(x2); cmg[3] = Q::template rep_bcast_uniform<3>(xm);
+                  } else {
 #pragma unroll
-                  for (int j = 0; j < 4; j++) { cd1[j] = Q::rep_bcast(x1, j); cd2[j] = Q::rep_bcast(x2, j); cmg[j] = Q::rep_bcast(xm, j); }
+                    for (int j = 0; j < 4; j++) { cd1[j] = Q::rep_bcast(x1, j); cd2[j] = Q::rep_bcast(x2, j); cmg[j] = Q::rep_bcast(xm, j); }
+                  }
                 }
                 if (c == 0) cnt.ls_evals++;
 #ifdef LM_LS_TRACE

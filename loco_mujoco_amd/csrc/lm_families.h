@@ -29,6 +29,15 @@
 // contacts with a Hessian block has condim > 3 (lm_core.h kHessEnvVote: same numbers either way). 0: every slot by its own condim, as before.
 #define LM_HESS_ENV_VOTE 1
 #endif
+#ifndef LM_DPP_BCAST
+// 1: in the four-replica kernels compiled for the elliptic cone (the quadruped's regular, fused and replay kernels) the exchanges
+// between the replicas of an environment (the line search's four points, the floor pass's contact counts) and between the lanes of a
+// quad (the pair pass) are DPP moves — row_newbcast, row_ror, quad_perm: VALU, no address arithmetic, no LDS wait — instead of
+// ds_bpermute through the LDS crossbar (lm_step.h QuadDppT::kDppBcast, lm_core.h kDppBcast: same values either way). 0: ds_bpermute
+// everywhere, as before. The sixteen-replica and the plain layout, the pyramidal families, the generic family and the forward-only
+// kernels keep ds_bpermute (their objects do not change with the switch).
+#define LM_DPP_BCAST 1
+#endif
 // One row per family: X(id, MC, NS, RK4, CONE, NM, PM, flags) of struct Family. Ids 1 and 3 (four contact slots per chain) went in round 5.
 // A family listed here and not in FAMILIES of csrc/Makefile, or the reverse, fails when the library is linked: no checker is needed.
 #define LM_GENERIC_FAMILY 6

@@ -111,6 +111,28 @@ struct QuadDppT {
     const int lane = (int)((__lane_id() & ~3u) | (unsigned)src);
     return __int_as_float(__builtin_amdgcn_ds_bpermute(lane << 2, __float_as_int(x)));
   }
+  // The same exchanges as DPP moves, for the four-replica layout only (lm_families.h LM_DPP_BCAST; lm_core.h picks these members up
+  // where a policy has them — the CPU emulator's has not — and keeps rep_bcast / quad_read otherwise). A DPP move reads the source
+  // lane's register in the VALU: no address, no LDS instruction, no lgkmcnt wait. Every source lane must be ACTIVE where these are
+  // called (an inactive source reads as 0 under bound_ctrl): the call sites say why it is.
+  static constexpr bool kDppBcast = LM_DPP_BCAST != 0 && REP == 4;
+  // the value replica J holds of an x that is uniform over each quad (a result of sum()): any lane of the quad 4J .. 4J+3 of the
+  // 16-lane row — row_newbcast:4J = 0x150 + 4J
+  template <int J> static __device__ __forceinline__ float rep_bcast_uniform(float x) {
+    static_assert(REP == 4 && J >= 0 && J < 4, "four replicas in a 16-lane row");
+    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), 0x150 + 4 * J, 0xF, 0xF, true));
+  }
+  // x of the same chain's lane in another replica: K = 1, 2, 3 visit each of the other three replicas once (row_ror:4K = 0x120 + 4K;
+  // WHICH replica the caller learns from the value itself — it sends its replica number along)
+  template <int K> static __device__ __forceinline__ int rep_rot(int x) {
+    static_assert(REP == 4 && K >= 1 && K < 4, "four replicas in a 16-lane row");
+    return __builtin_amdgcn_mov_dpp(x, 0x120 + 4 * K, 0xF, 0xF, true);
+  }
+  // x of lane K of my quad — quad_perm:[K,K,K,K] = K * 0x55
+  template <int K> static __device__ __forceinline__ float quad_bcast(float x) {
+    static_assert(K >= 0 && K < 4, "a quad has four lanes");
+    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), K * 0x55, 0xF, 0xF, true));
+  }
   static __device__ __forceinline__ void quad_sync() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); }
   // replicas hand records to each other through the lane memory they share (contact slots, row states). The lanes of
   // a wave run in lock step and the LDS executes a wave's instructions in order, so no hardware wait is needed, but
