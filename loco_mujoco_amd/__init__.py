@@ -10,6 +10,7 @@ __version__ = "0.1.0"
 
 from .environments import (Atlas, GymnasiumWrapper, HumanoidMuscle, HumanoidMuscle4Ages, HumanoidTorque,
                            HumanoidTorque4Ages, LocoEnv, Talos, UnitreeA1, UnitreeG1, UnitreeH1)
+from .vector import LocoVectorEnv
 
 
 def get_all_task_names():

@@ -2,7 +2,8 @@
 Gymnasium front-end (reference: ``loco_mujoco/environments/gymnasium.py:11-173``): 5-tuple ``step``
 with ``truncated`` always False, ``reset(seed, options) -> (obs, {})``, float64 Box spaces.
 ``gymnasium`` itself is optional: without it the wrapper is a plain class with the same methods and
-``make("LocoMujoco", env_name=...)`` below stands in for ``gym.make``.
+``make("LocoMujoco", env_name=...)`` below stands in for ``gym.make``. The batched surface on device tensors is
+:class:`loco_mujoco_amd.vector.LocoVectorEnv` (``make_vec`` below / the registration's ``vector_entry_point``).
 """
 
 import numpy as np
@@ -96,8 +97,20 @@ def make(env_id, env_name=None, **kwargs):
     return GymnasiumWrapper(env_name, **kwargs)
 
 
+def make_vec(env_id, env_name=None, num_envs=1, **kwargs):
+    """Stand-in for ``gymnasium.make_vec("LocoMujoco", env_name=..., num_envs=...)`` when gymnasium is absent: the batched surface on
+    device tensors (:class:`loco_mujoco_amd.vector.LocoVectorEnv`)."""
+    assert env_id == "LocoMujoco"
+    from ..vector import LocoVectorEnv
+    return LocoVectorEnv(env_name, num_envs, **kwargs)
+
+
 if _gym is not None:                    # pragma: no cover
     try:
-        _gym.register("LocoMujoco", entry_point="loco_mujoco_amd.environments.gymnasium:GymnasiumWrapper")
+        try:
+            _gym.register("LocoMujoco", entry_point="loco_mujoco_amd.environments.gymnasium:GymnasiumWrapper",
+                          vector_entry_point="loco_mujoco_amd.vector:LocoVectorEnv")
+        except TypeError:               # a gymnasium from before vector entry points: the single-environment registration as it was
+            _gym.register("LocoMujoco", entry_point="loco_mujoco_amd.environments.gymnasium:GymnasiumWrapper")
     except Exception:
         pass
