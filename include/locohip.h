@@ -257,6 +257,8 @@ int lm_step_pinned(lm_batch* b, const double* action, int slot);
    observation returned for that step is the fresh one. */
 int lm_set_reset_table(lm_batch* b, const float* rows, int n_rows, uint64_t seed, int64_t global_env_offset);
 int lm_set_auto_reset(lm_batch* b, int enabled, int horizon);
+/* Setting, reading and restarting environments from DEVICE memory, on a stream: include/locostate.h (the ls_ names, served by this
+   library; a restart on request is the restart described above, for the environments of a mask). */
 
 /* n_steps control steps entirely on the device. action_mode 0: zero action; 1: a ~ U(-1,1)^nu from
    the counter-based RNG, keyed by (seed, global env id, the batch's count of control steps so far, action index).

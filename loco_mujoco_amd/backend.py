@@ -75,6 +75,12 @@ _PROTOTYPES = {
     "lm_snapshot_export": (_I, [_P, _P, _P, _LL]), "lm_snapshot_import": (_I, [_P, _P, _P, _LL]),
 }
 EXPORTS = list(_PROTOTYPES)
+# THE prototypes of include/locostate.h (state on device buffers; the same library, a header and a prefix of its own), stated once
+_STATE_PROTOTYPES = {
+    "ls_get_state_device": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I]), "ls_set_state_device": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I]),
+    "ls_restart_device": (_I, [_P, _P, _P, _P, _I]),
+}
+STATE_EXPORTS = list(_STATE_PROTOTYPES)
 
 _lib = None
 
@@ -92,7 +98,7 @@ def load_library():
         raise BackendError("HIP library not built: %s is missing (run `python -c 'import __graft_entry__ as g; "
                            "g.build()'` or `make -C loco_mujoco_amd/csrc`). There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in _PROTOTYPES.items():
+    for name, (restype, argtypes) in list(_PROTOTYPES.items()) + list(_STATE_PROTOTYPES.items()):
         fn = getattr(lib, name)
         fn.restype = restype          # (c_int is also what ctypes assumes)
         if argtypes is not None:
@@ -457,7 +463,51 @@ def check_terminal_obs_args(n, nobs, out):
                              say={"shape": "%(who)s: %(name)s must be %(shape)s, not %(got_tuple)s"})
 
 
-SNAPSHOT_BLOB_HEADER = 64        # bytes in front of the payload of lm_snapshot_export (include/locohip.h)
+def _check_device_mask(who, mask, n):
+    """An environment mask on the device: uint8 or bool [n] (a non-zero byte selects), or a raw device pointer."""
+    dtype = "bool" if "bool" in str(getattr(mask, "dtype", "")) else "uint8"
+    _check_device_buffer(who, "mask", mask, (n,), dtype, say={"dtype": "%(who)s: %(name)s must be uint8 or bool, not %(got)s"})
+
+
+def check_get_state_device_args(n, nv, na, ngoal, qpos=None, qvel=None, act=None, goal=None, ep_step=None, ep_count=None):
+    """The argument checks of :meth:`HipBatch.get_state_device`, without a device: raises ValueError. Every output is optional and is a
+    described object (torch tensor), which is checked — ``qpos`` / ``qvel`` float32 [n, nv], ``act`` float32 [n, na], ``goal`` float32
+    [n, ngoal], ``ep_step`` / ``ep_count`` int32 [n] (uint32 passes as well), contiguous, on the device — or a raw device pointer (int),
+    which is taken as given. What only the library can know (no output at all, ``act`` for a model without activations) is left to it."""
+    who = "get_state_device"
+    for name, x, shape, dtype in (("qpos", qpos, (n, nv), "float32"), ("qvel", qvel, (n, nv), "float32"), ("act", act, (n, na), "float32"),
+                                  ("goal", goal, (n, ngoal), "float32"), ("ep_step", ep_step, (n,), "int32"), ("ep_count", ep_count, (n,), "int32")):
+        if x is not None and not (name == "act" and na == 0):
+            _check_device_buffer(who, name, x, shape, dtype)
+
+
+def check_state_device_args(n, nv, na, ngoal, nobs, qpos, qvel, act=None, goal=None, mask=None, obs=None):
+    """The argument checks of :meth:`HipBatch.set_state_device`, without a device: raises ValueError. ``qpos`` and ``qvel`` are both
+    needed; buffers are described objects (torch tensors), which are checked — ``qpos`` / ``qvel`` float32 [n, nv], ``act`` float32
+    [n, na], ``goal`` float32 [n, ngoal], ``mask`` uint8 or bool [n], ``obs`` float32 [n, nobs], contiguous, on the device — or raw device
+    pointers (ints), which are taken as given. ``act`` for a model without activations is left to the library to refuse."""
+    who = "set_state_device"
+    for name, x in (("qpos", qpos), ("qvel", qvel)):
+        if x is None:
+            raise ValueError("%s: %s is None (a state is positions and velocities)" % (who, name))
+    for name, x, shape in (("qpos", qpos, (n, nv)), ("qvel", qvel, (n, nv)), ("act", act, (n, na)), ("goal", goal, (n, ngoal)), ("obs", obs, (n, nobs))):
+        if x is not None and not (name == "act" and na == 0):
+            _check_device_buffer(who, name, x, shape, "float32")
+    if mask is not None:
+        _check_device_mask(who, mask, n)
+
+
+def check_restart_device_args(n, nobs, mask=None, obs=None):
+    """The argument checks of :meth:`HipBatch.restart_device`, without a device: raises ValueError. ``mask`` uint8 or bool [n], ``obs``
+    float32 [n, nobs] — described objects (torch tensors), which are checked, or raw device pointers (ints), which are taken as given."""
+    who = "restart_device"
+    if mask is not None:
+        _check_device_mask(who, mask, n)
+    if obs is not None:
+        _check_device_buffer(who, "obs", obs, (n, nobs), "float32")
+
+
+SNAPSHOT_BLOB_HEADER = 64       # bytes in front of the payload of lm_snapshot_export (include/locohip.h)
 
 
 def check_restore_args(n, src=None, mask=None, snapshot=None, batch=None):
@@ -655,6 +705,36 @@ class HipBatch:
         ``done.bool()`` mixes truncation and restarts into the terminal flag; mask the bits."""
         _check(self._lib.lm_step_device(self._h, _dev_ptr(action), _dev_ptr(obs), _dev_ptr(reward), _dev_ptr(done),
                                         _stream_ptr(stream), int(bool(sync))))
+
+    def get_state_device(self, qpos=None, qvel=None, act=None, goal=None, ep_step=None, ep_count=None, stream=None, sync=True):
+        """The state of every environment into DEVICE buffers, one launch (``ls_get_state_device``): ``qpos`` / ``qvel`` float32
+        [n, nv], ``act`` float32 [n, na], ``goal`` float32 [n, ngoal], ``ep_step`` int32 [n], ``ep_count`` int32 / uint32 [n] — torch
+        tensors or raw device pointers, each optional, not all None. ``stream`` / ``sync`` as in :meth:`step_device`: queued behind
+        whatever the batch has in flight; ``sync=False`` waits for nothing."""
+        check_get_state_device_args(self.n, self.nv, self.na, self.ngoal, qpos, qvel, act, goal, ep_step, ep_count)
+        _check(self._lib.ls_get_state_device(self._h, _dev_ptr(qpos), _dev_ptr(qvel), _dev_ptr(act), _dev_ptr(goal), _dev_ptr(ep_step),
+                                             _dev_ptr(ep_count), _stream_ptr(stream), int(bool(sync))))
+
+    def set_state_device(self, qpos, qvel, act=None, goal=None, mask=None, obs=None, stream=None, sync=True):
+        """:meth:`set_state` from DEVICE rows, one launch (``ls_set_state_device``): for every environment whose ``mask`` byte (uint8 or
+        bool [n]; None: all) is non-zero, ``qpos`` / ``qvel`` float32 [n, nv] are written, warm start, self-collision slack and the
+        episode's step are cleared and the activations zeroed — or set from ``act`` [n, na]; ``goal`` [n, ngoal] sets the goal. The
+        observation of the new state is written for those environments into ``obs`` float32 [n, nobs] (the kernel's column order,
+        foot-force columns 0), or into the batch's own last-step row when None, so ``rollout_policy(obs0=None)`` is valid afterwards.
+        The episode count, the flags and the reward / done rows stay. ``stream`` / ``sync`` as in :meth:`step_device`."""
+        check_state_device_args(self.n, self.nv, self.na, self.ngoal, self.nobs, qpos, qvel, act, goal, mask, obs)
+        _check(self._lib.ls_set_state_device(self._h, _dev_ptr(qpos), _dev_ptr(qvel), _dev_ptr(act), _dev_ptr(goal), _dev_ptr(mask),
+                                             _dev_ptr(obs), _stream_ptr(stream), int(bool(sync))))
+
+    def restart_device(self, mask=None, obs=None, stream=None, sync=True):
+        """Restart the masked environments (uint8 or bool [n] on the device; None: all) exactly as the step kernel restarts an episode
+        that ended (``ls_restart_device``): the episode count advances, the reset-table row is the one drawn from (seed, global
+        environment id, episode count), state and goal come from it, the model variant / the compiler's model and the randomised
+        joint parameters are redrawn. Needs :meth:`set_reset_table`; :meth:`set_auto_reset` need not be on. ``obs`` as in
+        :meth:`set_state_device`. Not touched: the collider's cache, the flags, the reward / done rows, the count of control steps,
+        the statistics. ``stream`` / ``sync`` as in :meth:`step_device`."""
+        check_restart_device_args(self.n, self.nobs, mask, obs)
+        _check(self._lib.ls_restart_device(self._h, _dev_ptr(mask), _dev_ptr(obs), _stream_ptr(stream), int(bool(sync))))
 
     def set_dof_params(self, damping=None, stiffness=None, frictionloss=None, mask=None):
         """Per-environment joint parameters [n, nv] (domain randomisation); None leaves a parameter as it is."""

@@ -4,6 +4,8 @@
 #include "lm_step.h"
 #include "lm_compile.h"
 #include "lm_snapshot.h"
+#include "lm_state_io.h"
+#include "../../include/locostate.h"
 #include "lm_model_parse.h"
 #include "lm_policy.h"
 #include <memory>
@@ -28,6 +30,7 @@ struct lm_model {
   // neighbour lists, body pairs, adjacency blocks of the hull vertices; n_gpt_floats: size of the geom-pair table (0: no self-collision pairs)
   float *d_cm, *d_gt, *d_mt, *d_gpt, *d_meshv, *d_meshn, *d_bpt, *d_meshadj; int n_gpt_floats;
   std::vector<float> nominal;  // [3][nv] damping | stiffness | frictionloss of the model
+  int *d_qobs, *d_vobs;        // [nv] observation column of qpos[d] / qvel[d], -1: not observed (lm_model_parse.h; read by lm_state_io.h)
   lm::Params P; Task T;
   int family;                // the kernel family that serves the model (lm_families.h pick_family; -1: none is compiled for it)
   bool root_limited;         // a root dof with an active-able limit (lm_batch_set_replay)
@@ -332,6 +335,10 @@ int lm_model_create(const double* cmod, size_t n, int device, lm_model** out) {
   const lmk::ModelFacts facts = {pm.T.max_links, pm.T.max_contacts, pm.integrator, pm.cone, pm.T.na, pm.T.npair, pm.T.all_pyr3 != 0, pm.root_xyz};
   m->family = lmk::pick_family(facts, generic);
   if (m->family < 0) return fail(lmk::no_family_reason(facts));      // refused HERE, not at the first launch
+  for (auto [host, dev] : {std::make_pair(&pm.qobs, &m->d_qobs), std::make_pair(&pm.vobs, &m->d_vobs)}) {
+    HIPCHK(hipMalloc(dev, sizeof(int) * (host->size() ? host->size() : 1)));
+    HIPCHK(hipMemcpy(*dev, host->data(), sizeof(int) * host->size(), hipMemcpyHostToDevice));
+  }
   if (upload(pm.cm, &m->d_cm) || upload(pm.gt, &m->d_gt) || (!pm.mt.empty() && upload(pm.mt, &m->d_mt)) || upload(pm.gpt, &m->d_gpt) ||
       upload(pm.meshv, &m->d_meshv) || upload(pm.meshn, &m->d_meshn) || upload(pm.bpt, &m->d_bpt) || upload(pm.meshadj, &m->d_meshadj)) return 1;
   lm::Params& P = m->P;
@@ -355,6 +362,7 @@ int lm_model_create(const double* cmod, size_t n, int device, lm_model** out) {
 void lm_model_destroy(lm_model* m) {
   if (!m) return;
   for (float* p : {m->d_cm, m->d_gt, m->d_gpt, m->d_meshv, m->d_meshn, m->d_bpt, m->d_meshadj, m->d_mt}) if (p) (void)hipFree(p);
+  for (int* p : {m->d_qobs, m->d_vobs}) if (p) (void)hipFree(p);
   delete m;
 }
 
@@ -1215,6 +1223,48 @@ int lm_set_reset_table(lm_batch* b, const float* rows, int n_rows, uint64_t seed
   b->table_rows = n_rows; b->seed = seed; b->env_offset = global_env_offset;
   b->var_rows = 0;                 // a new table: the variant no longer follows the row until lm_set_variant_rows says so
   return 0;
+}
+
+// ---- state on device buffers (include/locostate.h ls_get_state_device, ls_set_state_device, ls_restart_device; the kernels: lm_state_io.h)
+static lmio::State io_state(const lm_batch* b) {
+  const Task& T = b->m->T;
+  return {b->N, T.nv, T.na, T.ngoal, T.nobs, T.ngrf, b->qpos, b->qvel, b->warm, b->act, b->goal, b->slack, b->ep_step, b->ep_count, b->premark,
+          b->m->d_qobs, b->m->d_vobs};
+}
+
+int ls_get_state_device(lm_batch* b, float* d_qpos, float* d_qvel, float* d_act, float* d_goal, int32_t* d_ep_step, uint32_t* d_ep_count,
+                        void* stream, int sync) {
+  if (!b) return fail("null batch");
+  // every argument is checked before the launch: a refused call launches nothing
+  if (!d_qpos && !d_qvel && !d_act && !d_goal && !d_ep_step && !d_ep_count) return fail("ls_get_state_device: every output is null (nothing to read)");
+  if (d_act && !b->act) return fail("ls_get_state_device: d_act given, but the model has no activation states");
+  HIPCHK(hipSetDevice(b->m->device));
+  const lmio::GatherArgs a = {io_state(b), d_qpos, d_qvel, d_act, d_goal, d_ep_step, d_ep_count};
+  return on_stream(b, stream, sync, [&](hipStream_t s) { lmio::launch_gather(a, s); return 0; });
+}
+
+int ls_set_state_device(lm_batch* b, const float* d_qpos, const float* d_qvel, const float* d_act, const float* d_goal, const uint8_t* d_mask,
+                        float* d_obs, void* stream, int sync) {
+  if (!b) return fail("null batch");
+  if (!d_qpos || !d_qvel) return fail("ls_set_state_device: d_qpos and d_qvel are both needed (a state is positions and velocities)");
+  if (d_act && !b->act) return fail("ls_set_state_device: d_act given, but the model has no activation states");
+  HIPCHK(hipSetDevice(b->m->device));
+  const lmio::ScatterArgs a = {io_state(b), d_qpos, d_qvel, d_act, b->m->T.ngoal > 0 ? d_goal : nullptr, d_mask, d_obs ? d_obs : b->obs};
+  return on_stream(b, stream, sync, [&](hipStream_t s) { lmio::launch_scatter(a, s); return 0; });
+}
+
+int ls_restart_device(lm_batch* b, const uint8_t* d_mask, float* d_obs, void* stream, int sync) {
+  if (!b) return fail("null batch");
+  if (b->table_rows <= 0 || !b->table) return fail("ls_restart_device needs a reset table (lm_set_reset_table)");
+  HIPCHK(hipSetDevice(b->m->device));
+  const lmio::RestartArgs a = {io_state(b), b->table, b->table_rows, b->seed, b->env_offset, b->mc_ib ? b->vdirty : nullptr, b->var, b->nvar, b->var_rows,
+                               b->dofprm, b->dofprm ? b->drspec : nullptr, d_mask, d_obs ? d_obs : b->obs};
+  return on_stream(b, stream, sync, [&](hipStream_t s) {
+    lmio::launch_restart(a, s);
+    // the restarted environments get their fresh model before the next launch (stream order), as behind a step launch (queue_steps)
+    if (b->mc_ib) compile_models(b, nullptr, 0, s);
+    return 0;
+  });
 }
 
 int lm_set_auto_reset(lm_batch* b, int enabled, int horizon) {

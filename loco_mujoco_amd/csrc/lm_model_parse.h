@@ -14,6 +14,7 @@ struct ParsedModel {
   bool root_limited;         // a root dof with an active-able limit (lm_batch_set_replay)
   bool root_xyz;             // the root's first three dofs are slides along +x, +y, +z in a root frame that is the world's (lm_core.h ROOT_XYZ)
   std::vector<float> nominal;      // [3][nv] damping | stiffness | frictionloss of the model
+  std::vector<int> qobs, vobs;     // [nv] observation column of qpos[d] / qvel[d] (the dof records' LM_D_QOBS / LM_D_VOBS), -1: not observed
   // constant, geom, muscle (empty: no muscles), geom-pair (n_gpt_floats: without its padding), hull-vertex, neighbour, body-pair, adjacency tables
   std::vector<float> cm, gt, mt, gpt, meshv, meshn, bpt, meshadj; int n_gpt_floats;
 };
@@ -63,10 +64,15 @@ inline bool parse_model(const double* cmod, size_t n, ParsedModel* out, std::str
   T.na = n_muscle;
   const int nv = (int)cmod[LM_H_NV];
   m.nominal.assign((size_t)3 * nv, 0.0f);
+  m.qobs.assign((size_t)(nv > 0 ? nv : 0), -1); m.vobs.assign((size_t)(nv > 0 ? nv : 0), -1);
+  const int nobs_h = (int)cmod[LM_H_NOBS];
   auto put = [&](const float* blk, int stride) {
     const int d = (int)blk[LM_D_DOF * stride];
     if (d < 0 || d >= nv) return;
     m.nominal[d] = blk[LM_D_DAMP * stride]; m.nominal[nv + d] = blk[LM_D_STIFF * stride]; m.nominal[2 * nv + d] = blk[LM_D_FLOSS * stride];
+    // (a column outside the observation row counts as not observed: lm_state_io.h writes through these maps)
+    const int iq = (int)blk[LM_D_QOBS * stride], iv = (int)blk[LM_D_VOBS * stride];
+    m.qobs[d] = (iq >= 0 && iq < nobs_h) ? iq : -1; m.vobs[d] = (iv >= 0 && iv < nobs_h) ? iv : -1;
   };
   for (int i = 0; i < 6; i++) put(cm.data() + LM_R_DOFS + i * LM_D_SIZE, 1);
   for (int c = 0; c < LM_NCHAIN; c++) {

@@ -6,7 +6,8 @@ episode ended in, running returns and lengths. The library reads what a step wro
 the library is missing this module raises.
 
 Out of scope: NEXT_STEP autoreset; observation / reward normalisation wrappers (:class:`backend.ObsNorm` stays the per-rollout tool);
-partial host resets (``reset`` restarts every environment; single environments restart on the device).
+partial HOST resets (``reset()`` restarts every environment on the host; ``reset(options={"reset_mask": m})`` restarts chosen ones on the
+device, from the reset table).
 """
 
 import ctypes as C
@@ -157,7 +158,9 @@ class LocoVectorEnv(_VectorEnv):
     elsewhere, with ``_episode`` the same mask. Returns are summed in float32 in step order.
 
     The tensors returned are VIEWS of a ring of two result sets: what a step returned stays intact through the next ``step()`` — so
-    ``(obs, next_obs)`` pairs are valid — and is overwritten by the one after it. ``copy=True`` returns clones.
+    ``(obs, next_obs)`` pairs are valid — and is overwritten by the one after it. A partial reset (``reset(options={"reset_mask": m})``) is the exception: it replaces the
+    masked rows of the ``obs`` the last ``step()`` returned IN PLACE, so a caller that still needs that tensor as the successor of a
+    transition clones it first. ``copy=True`` returns clones.
 
     ``seed`` keys the device-side restart draws, ``horizon`` (None: the task's) truncates episodes; ``make_kwargs`` go to
     ``LocoEnv.make``. Refused, with the reason: several models in one batch, a reward evaluated on the host, ``num_envs < 1``."""
@@ -202,6 +205,7 @@ class LocoVectorEnv(_VectorEnv):
             self._raw_obs = torch.zeros((n, nobs), dtype=torch.float32, device=dev)
             self._raw_final = torch.zeros((n, nobs), dtype=torch.float32, device=dev)
         self._started = False
+        self._reset_obs = None          # the observation of a full reset() until the first step() replaces it
 
     @staticmethod
     def _index_of(device):
@@ -229,8 +233,18 @@ class LocoVectorEnv(_VectorEnv):
     def reset(self, *, seed=None, options=None):
         """The wrapped environment's host ``reset()``: every environment starts a new episode; returns ``(obs, {})`` with the
         observation uploaded once as float32 [num_envs, nobs]. A given ``seed`` re-keys the device-side restart draws; like the
-        single-environment wrapper's, it does not touch ``np.random``, which the host reset draws from."""
+        single-environment wrapper's, it does not touch ``np.random``, which the host reset draws from.
+
+        ``options={"reset_mask": m}`` is Gymnasium's PARTIAL reset, and stays on the device: ``m`` is a bool / uint8 device tensor
+        [num_envs] (a numpy mask is uploaded); the masked environments restart as the step kernel restarts an episode that ended
+        (:meth:`HipBatch.restart_device`: the next row of the reset table under the environment's own draw, episode count + 1), queued
+        on torch's current stream; their running return and length start from zero. Nothing waits on the host and there is no host
+        reset. Returns ``(obs, {})``: the current result set's observation — what the last ``step()`` returned (after a full
+        ``reset()``: what that returned) — with the masked rows replaced IN PLACE by the new episodes' first observations. Like
+        ``step()`` it bypasses ``LocoEnv``'s host mirrors of the state. Takes no ``seed``."""
         import torch
+        if options is not None and options.get("reset_mask") is not None:
+            return self._reset_masked(options["reset_mask"], seed)
         torch.cuda.synchronize(self.device)          # THE host wait of this class: steps still queued finish before the host restarts everything
         if seed is not None:
             self._arm(int(seed))
@@ -240,7 +254,58 @@ class LocoVectorEnv(_VectorEnv):
             self._run_return.zero_()
             self._run_length.zero_()
         self._started = True
+        self._reset_obs = obs
         return obs, {}
+
+    def _reset_masked(self, m, seed):
+        import torch
+        if seed is not None:
+            raise ValueError("LocoVectorEnv.reset: a partial reset takes no seed (the restart draws stay keyed as they are)")
+        if not self._started:
+            raise RuntimeError("call reset() before a partial reset")
+        env, b = self._env, self._env.backend
+        n = self.num_envs
+        if not hasattr(m, "data_ptr"):
+            m = torch.from_numpy(np.ascontiguousarray(np.asarray(m).reshape(-1) != 0)).to(self.device)
+        if tuple(m.shape) != (n,) or m.dtype not in (torch.bool, torch.uint8) or not m.is_cuda or not m.is_contiguous():
+            raise ValueError("LocoVectorEnv.reset: reset_mask must be a contiguous bool or uint8 device tensor [%d], not %s %s"
+                             % (n, m.dtype, list(m.shape)))
+        if env._pending_state:
+            env._upload_state()
+        r = self._ring[self._slot]
+        raw_obs = r.obs if self._perm is None else self._raw_obs
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            mb = m if m.dtype == torch.bool else m != 0
+            b.restart_device(m, obs=raw_obs, stream=stream, sync=False)
+            if self._perm is not None:
+                torch.index_select(raw_obs, 1, self._perm, out=r.obs)
+            if self._reset_obs is not None:
+                # no step since the full reset: the rows that no partial reset has replaced are the full reset's. They are kept in a
+                # tensor of their own, outside the ring (torch.where makes a new one), so the next partial reset finds them again
+                self._reset_obs = torch.where(mb[:, None], r.obs, self._reset_obs)
+                r.obs.copy_(self._reset_obs)
+            self._run_return.masked_fill_(mb, 0.0)
+            self._run_length.masked_fill_(mb, 0)
+            obs = r.obs.clone() if self._copy else r.obs
+        return obs, {}
+
+    def state(self):
+        """The full state of every environment as device tensors, queued on torch's current stream and waiting for nothing
+        (:meth:`HipBatch.get_state_device`): ``{"qpos": float32 [n, nv], "qvel": float32 [n, nv], "ep_step": int32 [n]}`` — the root's
+        horizontal position included, which no observation shows. Fresh tensors at every call. Read from the device batch, not from
+        ``LocoEnv``'s host mirrors (as ``step()``)."""
+        import torch
+        env, b = self._env, self._env.backend
+        if env._pending_state:
+            env._upload_state()
+        n = self.num_envs
+        with torch.cuda.device(self.device):
+            out = {"qpos": torch.empty((n, b.nv), dtype=torch.float32, device=self.device),
+                   "qvel": torch.empty((n, b.nv), dtype=torch.float32, device=self.device),
+                   "ep_step": torch.empty(n, dtype=torch.int32, device=self.device)}
+            b.get_state_device(stream=torch.cuda.current_stream(self.device).cuda_stream, sync=False, **out)
+        return out
 
     def step(self, actions):
         import torch
@@ -251,6 +316,7 @@ class LocoVectorEnv(_VectorEnv):
         _check_device_buffer("LocoVectorEnv.step", "actions", actions, (n, b.nu), "float32", raw=False)
         if env._pending_state:
             env._upload_state()
+        self._reset_obs = None
         self._slot ^= 1
         r = self._ring[self._slot]
         raw_obs, raw_final = (r.obs, r.final_obs) if self._perm is None else (self._raw_obs, self._raw_final)
