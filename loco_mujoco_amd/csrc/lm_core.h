@@ -28,7 +28,7 @@
 #include <math.h>
 #include <type_traits>
 #include "../../include/lm_layout.h"
-#include "lm_families.h"      // (the A/B switches LM_HESS_ENV_VOTE, LM_DPP_BCAST)
+#include "lm_families.h"      // (the A/B switches LM_HESS_ENV_VOTE, LM_DPP_BCAST, LM_LS_FLOOR_SPLIT)
 
 #define LM_PAIR_PAD 0.03f     // metres added to the reach of the link-pair list (lowering.PAIR_PAD)
 #ifndef LM_DEV_COLD
@@ -42,6 +42,11 @@ LM_DEV float lm_u2f(unsigned x) { return __builtin_bit_cast(float, x); }
 // stale line of the CU's L1; the emulator keeps the plain forms
 #define LM_GLD64(p) (*reinterpret_cast<const unsigned long long*>(p))
 #define LM_GST64(p, v) (*reinterpret_cast<unsigned long long*>(p) = (v))
+#endif
+#ifndef LM_OPAQUE_ONE
+// the weight of a floor slot in the line search (kLsFloorSplit): the step kernel (lm_step.h) makes it a 1.0f the optimiser cannot fold, so
+// that the products with it stay where the products with a weight read from lane memory were; the emulator keeps the plain value
+#define LM_OPAQUE_ONE() 1.0f
 #endif
 #ifndef LM_LMEM_T
 #define LM_LMEM_T float       // element type of lane memory (A/B probe: `volatile float`)
@@ -3410,6 +3415,9 @@ LM_DEV void forward(const float* cm, int c, const Params& P, float* qr, float* v
   // collapsed quadruped — condim-6 feet and condim-3 shins in every pass — no longer execute the 6-wide and the 3-wide code one after
   // the other.
   constexpr bool kHessEnvVote = LM_HESS_ENV_VOTE != 0 && CONE != 0;
+  // The line search's slot loop in two (lm_families.h LM_LS_FLOOR_SPLIT): floor slots first, without the pair bookkeeping of
+  // slot_weight, then the self-contact slots as before. The kernels compiled for the elliptic cone with the pair pass only.
+  constexpr bool kLsFloorSplit = LM_LS_FLOOR_SPLIT != 0 && CONE > 0 && PAIRS;
   float qf_r[6], qf_c[MC];      // constraint forces in joint space
 #pragma unroll
   for (int i = 0; i < 6; i++) qf_r[i] = 0;
@@ -3949,10 +3957,15 @@ LM_DEV void forward(const float* cm, int c, const Params& P, float* qr, float* v
               if (getenv("LM_ROWS")) printf("      lane %d row %d alpha %.6g t %.6g x %.5g iR %.4g f %.3g limD %.4g xl %.5g\n", c, k, alpha, t, x, iR_c[k], ff_c[k], lim_D_c[k], xl);
 #endif
             }
-            for (int s = 0; s < nslot; s++) {
+            // The terms of one contact slot. FLOOR (kLsFloorSplit): a slot in front of nfloor is a floor contact, its pair code is 0 and
+            // slot_weight(s) exactly 1.0f: the opaque one stands for it — no read of SL_PART, none of the code arithmetic, and the two
+            // products and the sums behind them stay the operations they are with a weight from lane memory (x * 1.0f is exact).
+            float ls_one = 1.0f;
+            if constexpr (kLsFloorSplit) ls_one = LM_OPAQUE_ONE();
+            auto line_slot = [&](int s, auto floor_slot, float& c1, float& c2) {
+              constexpr bool FLOOR = decltype(floor_slot)::value;
               float Dj[6], fr[5], jar[6], jv[6];
               const int dim = (int)SL(s, SL_DIM);
-              float c1 = 0, c2 = 0;
               if (PYR3(dim)) {
                 const float D = SL(s, SL_D);
 #pragma unroll
@@ -3988,8 +4001,14 @@ LM_DEV void forward(const float* cm, int c, const Params& P, float* qr, float* v
 #ifdef LM_LS_TRACE
               if (getenv("LM_ROWS")) printf("      lane %d slot %d alpha %.6g c1 %.6g c2 %.6g\n", c, s, alpha, c1, c2);
 #endif
-              if (PAIRS) { const float wgt = slot_weight(s); c1 *= wgt; c2 *= wgt; }      // mirror slots: half each
-              a1 += c1; a2 += c2; am += fabsf(c1);
+              if constexpr (FLOOR) { c1 *= ls_one; c2 *= ls_one; }
+              else if (PAIRS) { const float wgt = slot_weight(s); c1 *= wgt; c2 *= wgt; }      // mirror slots: half each
+            };
+            if constexpr (kLsFloorSplit) {      // the order of the sums a1, a2, am is the one loop's
+              for (int s = 0; s < nfloor; s++) { float c1 = 0, c2 = 0; line_slot(s, std::true_type{}, c1, c2); a1 += c1; a2 += c2; am += fabsf(c1); }
+              for (int s = nfloor; s < nslot; s++) { float c1 = 0, c2 = 0; line_slot(s, std::false_type{}, c1, c2); a1 += c1; a2 += c2; am += fabsf(c1); }
+            } else {
+              for (int s = 0; s < nslot; s++) { float c1 = 0, c2 = 0; line_slot(s, std::false_type{}, c1, c2); a1 += c1; a2 += c2; am += fabsf(c1); }
             }
             d1 = g1 + alpha * q2 + Q::sum(a1 + w0 * r1);
             d2 = q2 + Q::sum(a2 + w0 * r2);

@@ -38,6 +38,14 @@
 // kernels keep ds_bpermute (their objects do not change with the switch).
 #define LM_DPP_BCAST 1
 #endif
+#ifndef LM_LS_FLOOR_SPLIT
+// 1: in the kernels compiled for the elliptic cone with the pair pass (the quadruped's regular, fused and replay kernels) the line
+// search visits the floor slots [0, nfloor) and the self-contact slots [nfloor, nslot) in loops of their own (lm_core.h kLsFloorSplit):
+// a floor slot's weight is an opaque 1.0f (lm_step.h LM_OPAQUE_ONE) instead of the slot's pair code read from lane memory and taken
+// apart — the same multiplies and the same sums in the same order, so the same numbers. 0: one loop over all slots, as before. Every
+// other family and the forward-only kernels keep the one loop (their objects do not change with the switch).
+#define LM_LS_FLOOR_SPLIT 1
+#endif
 // One row per family: X(id, MC, NS, RK4, CONE, NM, PM, flags) of struct Family. Ids 1 and 3 (four contact slots per chain) went in round 5.
 // A family listed here and not in FAMILIES of csrc/Makefile, or the reverse, fails when the library is linked: no checker is needed.
 #define LM_GENERIC_FAMILY 6

@@ -37,6 +37,10 @@
 // an integer the optimiser cannot see through (always 0): see lm_core.h `oz`
 __device__ __forceinline__ int lm_opaque_zero() { int z = 0; asm volatile("" : "+v"(z)); return z; }
 #define LM_OPAQUE_ZERO() lm_opaque_zero()
+// a 1.0f the optimiser cannot see through: a product with it stays a multiply (and fuses into the sum behind it as the product with a
+// weight read from lane memory does), see lm_core.h kLsFloorSplit
+__device__ __forceinline__ float lm_opaque_one() { float o = 1.0f; asm volatile("" : "+v"(o)); return o; }
+#define LM_OPAQUE_ONE() lm_opaque_one()
 // words of the convex collider's warm-start cache (lm_core.h mpr_convex_pair): agent-scope relaxed atomics — past the CU's L1, which the
 // lane that wrote the word one forward pass earlier does not share a coherent view with by default (loads could hit a stale line)
 #define LM_GLD64(p) __hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
